@@ -16,7 +16,8 @@ R rows over the ranks instead (strong scaling: rows/GPU = R / N).  `--batch 256 
 configs[3] / configs[4] (passes of 256 query rows: the dump is read once per 256 rows); `--dist mixture` swaps the
 i.i.d. dump for the mixture-of-4096-Gaussians + saturated-outlier dump (SURVEY.md 8d, config 4 data).
 
-After the configs[1] measurement (which alone is `value`), an N=1 run times three more workloads and appends them under
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.
+With --full, after the configs[1] measurement (which alone is `value`), an N=1 run times more workloads and appends them under
 `also` (skip with --no_also): `pq_opq96_ivf2p20_b64` (the reference's own index type -- OPQ96 + IVFPQ, 2^20 lists, nprobe 256 --
 resident in HBM), `e2e_mips_search` (host queries in, result dicts out through the python class the reference's
 callers use), `exact_b512_document` (configs[4]'s shape: batch 512, retrieval_unit=document => top_k doubled, title
@@ -27,9 +28,10 @@ and, inside the PQ leg, `e2e_mips_search` over the PQ index (the reference's shi
 
 Invoked as `python bench.py --gpus N` with N > 1 and no torchrun environment, it spawns the N ranks itself.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with `roofline` (the scan kernel: algorithmic
-bytes per launch / average launch duration from HIP events recorded around every full-scan launch on its stream) and
-`cpu_baseline` (a FAISS-CPU-shaped fp32 flat search on a bounded sample, rank 0, N=1 only).
+Prints ONE JSON line on rank 0 with `value`, `ms_per_step` and `roofline` (the scan kernel: algorithmic bytes per launch /
+average launch duration from HIP events recorded around every full-scan launch on its stream); --full adds recall@k against an
+independent fp64 brute force, `cpu_baseline` (a FAISS-CPU-shaped fp32 flat search on a bounded sample, rank 0, N=1 only) and
+`roofline.traffic` (a nested rocprofv3 FETCH_SIZE pass).
 """
 from __future__ import annotations
 
@@ -76,7 +78,12 @@ def parse():
     ap.add_argument("--trace_out", default="", help="write PATH: per timed full-scan launch the HIP-event duration and the rocprofv3 --kernel-trace dispatch "
                     "duration of the same workload on this box (tools/trace_out.py; `--dist anisotropic`: that leg), then exit")
     ap.add_argument("--recall_queries", type=int, default=64,
-                    help="queries of the last batch whose top-k is recomputed by an independent fp64 scan for recall@k")
+                    help="queries of the last batch whose top-k is recomputed by an independent fp64 scan for recall@k (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: recall@k against an independent fp64 brute force, the configs[3]/[4]/end-to-end "
+                         "sub-records, the CPU baselines and the nested rocprofv3 FETCH_SIZE pass (each still subject to its --no_* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -977,7 +984,7 @@ def make_line(args, world, weak, n_total, n_local, elapsed, scan_ms, scan_launch
                    "parallelism": f"range-shard x{world}", "scan_launches_per_step": launches_per_step},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "traffic_note": "not measured (--no_traffic / N > 1); rocprofv3 FETCH_SIZE passes are under profiles/",
+                     "traffic_note": "not measured (without --full, --no_traffic / N > 1); rocprofv3 FETCH_SIZE passes are under profiles/",
                      "kernel": kernel, "avg_launch_ms": avg_scan_s * 1e3, "launches": scan_launches,
                      "fused_ladder_stride": fused, "rows_read_by_the_launch": launch_rows,
                      "algorithmic_bytes_per_launch": alg_launch,
@@ -1016,6 +1023,16 @@ def independent_topk(shard_rows_ptr, n_local, id_base, xq, k, dev):
         o = torch.topk(cs, k, dim=1)
         best_s, best_i = o.values, torch.gather(ci, 1, o.indices)
     return best_s, best_i
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the arrays the last timed step handed its caller (ShardedSearcher.step: scores D, ids I, re-scored window
+    scores best, partner positions pred, status), one DIR/<name>.npy each -- fp32 stays fp32, everything else as float64 (exact
+    for every id and position).  [2B, k] values per array: a few KB."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 class _DevRows:
@@ -1079,7 +1096,10 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
     import __graft_entry__ as g
-    g.build()
+    # build only what is missing or stale: a tree that build() already left complete may be read-only to whoever measures it
+    # (the build's lock file is opened for writing); importing densephrases_amd below raises if libdph is unusable
+    if g._builder().needs_build():
+        g.build()
     one_gpu = world > 1 and os.environ.get("DPH_BENCH_ONE_GPU") == "1"       # rehearsal: every rank on cuda:0, gloo
     if one_gpu:
         local = 0
@@ -1220,6 +1240,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:     # (N > 1: the merged answer, the same on every rank)
+        dump_outputs(out, args.dump_outputs)
 
     # sanity of the timed result: every row of every timed step certified, planted rows first (a wrong-but-fast run
     # must not produce a number)
@@ -1246,7 +1268,7 @@ def main():
     # force in plain torch over this rank's shard; N > 1: the per-rank answers are all-gathered and merged on the host
     # (score desc, id asc) -- the merged answer of the timed step must equal that, id by id
     recall = None
-    if args.recall_queries > 0 and not args.no_check:
+    if args.full and args.recall_queries > 0 and not args.no_check:
         nq = min(args.recall_queries, B)
         sel = torch.cat([torch.arange(B // 2 - nq // 2, B // 2 + (nq + 1) // 2), B + torch.arange(nq)]).to(dev)
         xs = searcher.x[sel]
@@ -1290,7 +1312,7 @@ def main():
         if recall is not None:
             line.update(recall)
             line["recall_note"] = "id overlap with an independent fp64 brute force (plain torch) over the resident dump"
-        if world == 1 and not args.no_also and B == 64 and kind == 0 and args.rows == 0:     # the default configs[1] run only
+        if args.full and world == 1 and not args.no_also and B == 64 and kind == 0 and args.rows == 0:     # the default configs[1] run only
             # configs[3] / configs[4] / end-to-end, driver-timed in the same run (never part of `value`)
             also = {}
             for name, fn in (("e2e_mips_search", lambda: also_e2e(shard, args, n_total)),
@@ -1333,9 +1355,9 @@ def main():
                 also["pq_opq96_ivf2p20_skewed_b64"] = {"error": repr(e)[:300]}
             also["pq_opq96_ivf2p20_skewed_b64"]["leg_seconds"] = time.perf_counter() - t_leg
             line["also"] = also
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, n_total)
-        if world == 1 and not args.no_traffic:
+        if args.full and world == 1 and not args.no_traffic:
             searcher = None
             shard.close()                         # (idempotent) the nested pass needs the HBM
             torch.cuda.empty_cache()

@@ -106,7 +106,7 @@ def test_committed_bench_line_keeps_the_contract():
 def test_default_step_count_is_the_reference_benchmark_set_in_eval_batches():
     """the timed query count follows the reference's own benchmark set -- scripts/benchmark/data/
     nq_1000_dev_denspi.json, 1000 NQ-dev questions -- cut into eval batches of 64 (options.py eval_batch_size): 15 full batches, and
-    run_demo.py:329-352 excludes the first 5 batches from its timing.  (The file itself only exists next to the reference.)"""
+    run_demo.py:329-352 excludes the first 5 batches from its timing.  (tests/golden/nq_1000_dev_ids.json: the ids of that file's questions.)"""
     import sys
     import bench
     argv, sys.argv = sys.argv, ["bench.py"]
@@ -115,6 +115,23 @@ def test_default_step_count_is_the_reference_benchmark_set_in_eval_batches():
     finally:
         sys.argv = argv
     assert a.batch == 64 and a.warmup == 5
-    path = "/root/reference/scripts/benchmark/data/nq_1000_dev_denspi.json"
-    n_questions = len(json.load(open(path))["data"]) if os.path.exists(path) else 1000
-    assert n_questions == 1000 and a.steps == n_questions // a.batch
+    with open(os.path.join(ROOT, "tests", "golden", "nq_1000_dev_ids.json")) as f:
+        ids = json.load(f)["ids"]
+    n_questions = len(set(ids))
+    assert n_questions == len(ids) == 1000 and a.steps == n_questions // a.batch
+    assert not a.full and a.dump_outputs == ""                       # a plain run: the headline figure only
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array the timed step returns; fp32 stays fp32, ids / positions / status as float64"""
+    import numpy as np
+    import torch
+    import bench
+    out = {"D": torch.tensor([[1.5, -2.0]], dtype=torch.float32), "I": torch.tensor([[169_999_999, -1]], dtype=torch.int64),
+           "best": torch.tensor([[0.25, 3.0]], dtype=torch.float64), "pred": torch.tensor([[7, 9]], dtype=torch.int32),
+           "status": torch.tensor([0], dtype=torch.int32)}
+    bench.dump_outputs(out, str(tmp_path / "o"))
+    for name, t in out.items():
+        a = np.load(tmp_path / "o" / f"{name}.npy")
+        assert a.dtype == (np.float32 if name == "D" else np.float64) and a.shape == tuple(t.shape)
+        assert (a == t.numpy()).all()
