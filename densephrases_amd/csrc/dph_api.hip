@@ -1409,12 +1409,18 @@ static int search_dev_impl(dph_index* h, const float* x_dev, int64_t n, int k, i
         if (opt.top_out || opt.tau_ext) return fail(DPH_E_STATE, std::string(who) + ": the sharded two-phase entry points do not serve PQ indexes");
         if (!h->finalized) return fail(DPH_E_STATE, std::string(who) + ": call dph_index_finalize first");
         if (n == 0) return DPH_OK;
+        HIPCHK(hipSetDevice(h->device));
+        if (!h->counters) HIPCHK(hipMalloc((void**)&h->counters, 8 * sizeof(int)));
         h->stats = dph_search_stats{};
         h->stats.rows = (int32_t)n;
-        h->stats.certified_fast = (int32_t)n;
         h->stats_pending = false;
         const int rc = dph_pq_search_dev(h->pq, x_dev, n, k, pq_nprobe(h, nprobe), D_dev, I_dev, status_dev, (hipStream_t)stream);
-        return rc ? fail(rc, std::string(who) + ": " + dph_pq_error()) : DPH_OK;
+        if (rc) return fail(rc, std::string(who) + ": " + dph_pq_error());
+        // the rows' statuses, counted on the device: [0] uncertified, [1] non-finite (read back when dph_search_get_stats asks)
+        dph_launch_count_status(status_dev, n, h->counters, (hipStream_t)stream);
+        HIPCHK(hipGetLastError());
+        h->stats_pending = true;
+        return DPH_OK;
     }
     int rc = check_search_args(h, x_dev, n, k, nprobe, D_dev, I_dev, who);
     if (rc) return rc;
@@ -1450,6 +1456,7 @@ static int search_host_impl(dph_index* h, const float* x, int64_t n, int k, int 
         if (rc) return rc;
         int bad = 0, nf = 0;
         for (int32_t v : status) { bad += v == 1; nf += v == DPH_ROW_NONFINITE; }
+        h->stats_pending = false;        // (counted here from the copied statuses)
         h->stats.uncertified = bad;
         h->stats.nonfinite = nf;
         h->stats.certified_fast = (int32_t)n - bad - nf;
@@ -1473,7 +1480,8 @@ static int search_host_impl(dph_index* h, const float* x, int64_t n, int k, int 
     rc = read_counters(h, st, c);
     if (rc) return rc;
     h->stats.nonfinite = c[4];
-    h->stats.certified_fast = (int32_t)(n - c[0] - c[3]);
+    // (a non-finite row's stand-in is searched and certified like any row; the row is counted once, as non-finite)
+    h->stats.certified_fast = (int32_t)(n - c[0] - c[3] - c[4]);
     h->stats.certified_wide = c[0] - c[1] + c[3];
     h->stats.certified_reselect = c[3];
     int left = c[2];
@@ -1635,9 +1643,17 @@ int dph_search_get_stats(dph_index* h, dph_search_stats* out) {
         int c[5] = {0, 0, 0, 0, 0};
         HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemcpy(c, h->counters, sizeof(c), hipMemcpyDeviceToHost));
+        h->stats_pending = false;
+        if (h->pq) {                     // (search_dev_impl: the statuses the PQ search wrote, counted)
+            h->stats.uncertified = c[0];
+            h->stats.nonfinite = c[1];
+            h->stats.certified_fast = h->stats.rows - c[0] - c[1];
+            *out = h->stats;
+            return DPH_OK;
+        }
         h->stats.nonfinite = c[4];
         // c[3]: rows the first look could not certify and the wider look at the same bucket could (no re-scan)
-        h->stats.certified_fast = h->stats.rows - c[0] - c[3];
+        h->stats.certified_fast = h->stats.rows - c[0] - c[3] - c[4];      // (non-finite rows are counted once, as non-finite)
         h->stats.certified_wide = c[0] - c[1] + c[3];
         h->stats.certified_reselect = c[3];
         h->stats.exact_fallback = c[1] - c[2];

@@ -284,6 +284,7 @@ void dph_launch_gather_sample(const int8_t* db, int64_t n_rows, const int64_t* i
 void dph_launch_compact_failing(const int32_t* fail, int64_t n, int match, const float* x, int32_t* rows_out, int* count_out,
                                 float* x_out, int max_rows, hipStream_t st);
 void dph_launch_gather_rows(const float* x, const int32_t* rows, const int* count, float* x_out, int max_rows, hipStream_t st);
+void dph_launch_count_status(const int32_t* status, int64_t n, int* out, hipStream_t st);
 void dph_launch_retry_tau(const int* gate, int64_t n_max, const int32_t* rows, const int32_t* ik, const dph_qinfo* qinfo,
                           double rmax, double delta_max, float scale, int* tau_out, hipStream_t st);
 

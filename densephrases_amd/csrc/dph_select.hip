@@ -292,6 +292,21 @@ __global__ __launch_bounds__(256) void dph_gather_rows_kernel(const float* __res
 void dph_launch_gather_rows(const float* x, const int32_t* rows, const int* count, float* x_out, int max_rows, hipStream_t st) {
     if (max_rows > 0) hipLaunchKernelGGL(dph_gather_rows_kernel, dim3(max_rows), dim3(256), 0, st, x, rows, count, x_out);
 }
+// rows of a call whose status is DPH_ROW_UNCERTIFIED -> out[0], DPH_ROW_NONFINITE -> out[1] (the statistics of a device-pointer call)
+__global__ __launch_bounds__(1024) void dph_count_status_kernel(const int32_t* __restrict__ status, int64_t n, int* __restrict__ out) {
+    __shared__ int cnt[2];
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    int u = 0, f = 0;
+    for (int64_t r = threadIdx.x; r < n; r += 1024) { const int32_t v = status[r]; u += v == 1; f += v == DPH_ROW_NONFINITE; }
+    if (u) atomicAdd(&cnt[0], u);
+    if (f) atomicAdd(&cnt[1], f);
+    __syncthreads();
+    if (threadIdx.x < 2) out[threadIdx.x] = cnt[threadIdx.x];
+}
+void dph_launch_count_status(const int32_t* status, int64_t n, int* out, hipStream_t st) {
+    hipLaunchKernelGGL(dph_count_status_kernel, dim3(1), dim3(1024), 0, st, status, n, out);
+}
 // match = 0: rows whose flag is non-zero; otherwise rows whose flag equals `match`
 void dph_launch_compact_failing(const int32_t* fail, int64_t n, int match, const float* x, int32_t* rows_out, int* count_out,
                                 float* x_out, int max_rows, hipStream_t st) {

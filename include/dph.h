@@ -135,7 +135,9 @@ void*   dph_index_rows_dev(dph_index* h);
  * x: [n,768] fp32 row-major; D: [n,k] fp32 descending; I: [n,k] int64 global ids (id_base + local row);
  * fewer than k rows -> I = -1, D = -FLT_MAX (FAISS padding).  Exact inner product over the fp32
  * de-quantised rows, ties ordered (score desc, id asc).  Host-pointer form: synchronous, retries wider /
- * exact scans until every row is certified exact; returns DPH_E_UNCERTIFIED only if that is impossible.
+ * exact scans until every row is certified exact.  It returns DPH_E_UNCERTIFIED in one case: a row has more exact
+ * ties at its k-th place than the fp64 scan's hit buffer holds (2^20 per row); dph_search_stats.uncertified counts
+ * such rows and D / I must not be used.  Neither form ever answers such a row with success.
  * NON-FINITE query rows (a NaN / Inf element; index.py:195-200 hands FAISS whatever the encoder produced): FAISS' flat search
  * answers such a row with ids -1 / scores -FLT_MAX (no score compares greater than its heap's threshold) and the other rows as
  * ever.  Same here, on every index type: that row gets I = -1, D = -FLT_MAX, status DPH_ROW_NONFINITE (device forms) and is counted
@@ -145,8 +147,9 @@ int dph_search(dph_index* h, const float* x, int64_t n, int k, float* D, int64_t
 /* device-pointer form, asynchronous on `stream`, no host round trip: the first attempt, then -- gated by a
  * device-side count, a few empty launches when nothing failed -- a retry scan of the uncertified rows under a bound
  * derived from their own k-th best integer score, then the fp64 full scan for up to 32 rows that still fail.
- * status_dev [n] int32 receives 0 = certified exact, 1 = not certified (only if more than 32 rows needed the fp64
- * scan, or boundary ties exceed its 1 M-row buffer; dph_search settles those too), 3 = non-finite query row.  n <= 2^20. */
+ * status_dev [n] int32 receives 0 = certified exact, 1 = not certified, 3 = non-finite query row.  Status 1 comes
+ * back when more than 32 rows needed the fp64 scan (dph_search settles those) or when a row's boundary ties exceed the
+ * scan's 2^20-hit buffer (dph_search returns DPH_E_UNCERTIFIED for that row).  n <= 2^20. */
 int dph_search_dev(dph_index* h, const float* x_dev, int64_t n, int k, float* D_dev, int64_t* I_dev,
                    int32_t* status_dev, void* stream);
 /* statistics of the last search on the handle; after a device-pointer call this synchronises the device */

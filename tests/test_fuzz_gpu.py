@@ -487,3 +487,81 @@ def test_full_size_random_rounds(seed):
             np.testing.assert_array_equal(Dm[r][order], D[r][own], err_msg=f"{what} draw {di} row {r}")
             diff = Im[r][order] != I[r][own]
             assert not diff.any() or (D[r][own][diff] == D[r][own][-1]).all(), f"{what} draw {di} row {r}: ids differ away from a tie at the k-th place"
+
+
+# Full-size IVF / IVFPQ rounds: the suite's full-size coverage of these paths is tests/test_full_size_ivf_pq.py (fixed cases); these
+# rounds exist only under DPH_FUZZ_ROUNDS=n (max(1, n // 50) rounds each), with the checks of that module for every call.
+if ROUNDS:
+    @pytest.mark.parametrize("seed", _seeds([])[: max(1, ROUNDS // 50)])
+    def test_full_size_pq_random_rounds(seed):
+        import torch
+        from densephrases_amd.synth import synthetic_pq_shard
+        from tests.test_full_size_ivf_pq import _pq_queries, check_pq_call
+        rng = np.random.default_rng(seed)
+        skew = _pick(rng, ["", "zipf", "lognormal", "giant"])
+        nlist = int(_pick(rng, [1 << 16, 1 << 18, 1 << 20]))
+        M = int(_pick(rng, [48, 64, 96]))
+        n = int(_pick(rng, [50_000_000, 170_000_000]))
+        what = f"seed {seed}: PQ n {n} nlist {nlist} M {M} skew {skew!r}"
+        print(what)
+        s, A, cent, sizes, pqc, block = synthetic_pq_shard(n, nlist, M, return_parts=True, doc_len=100, skew=skew)
+        parts, notes = (sizes, A, cent, pqc, block), []
+        try:
+            for call in range(3):
+                n_q = int(rng.integers(1, 2101))
+                k = int(_pick(rng, [1, 10, 100, 200, 1024]))
+                nprobe = int(min(nlist, _pick(rng, [1, 5, 64, 256, 1024])))
+                x = _pq_queries(rng, A, cent, n_q)
+                bad = np.zeros(0, np.int64)
+                if n_q >= 3 and rng.random() < 0.5:
+                    bad = np.asarray([int(rng.integers(0, n_q))])
+                    x[bad[0], int(rng.integers(0, 768))] = np.nan
+                check_pq_call(s, parts, x, k, nprobe, bad, f"{what} | call {call}: n_q {n_q} k {k} nprobe {nprobe}", notes)
+        finally:
+            s.close()
+            del s
+            torch.cuda.empty_cache()
+
+    @pytest.mark.parametrize("seed", _seeds([])[: max(1, ROUNDS // 50)])
+    def test_full_size_ivf_random_rounds(seed):
+        import gc
+        import torch
+        from densephrases_amd import Shard
+        from densephrases_amd.ivf import make_list_major_resident
+        from densephrases_amd.synth import synthetic_rows
+        from tests._fullsize import gpu_ivf_flat_search_regenerated, regenerated_rows
+        from tests.test_full_size_ivf_pq import check_ivf_calls
+        rng = np.random.default_rng(seed)
+        kind = int(_pick(rng, [0, 1, 2, 3]))
+        nlist = int(_pick(rng, [1024, 4096, 16384]))
+        dump_seed = int(rng.integers(1, 1 << 30))
+        n = 170_000_000 // 32 * 32
+        what = f"seed {seed}: IVF n {n} kind {kind} dump seed {dump_seed} nlist {nlist}"
+        print(what)
+        gc.collect()
+        torch.cuda.empty_cache()
+        free, _ = torch.cuda.mem_get_info(0)
+        if free < 2 * n * 768 + (12 << 30):
+            pytest.skip(f"the list builder needs 2 x {n * 768} + 12 GiB bytes of free HBM; {free} bytes are free")
+        s = Shard(n, device=0)
+        try:
+            s.fill_synthetic(seed=dump_seed, kind=kind)
+            cent, assign = make_list_major_resident(s, nlist, seed=seed)
+            s.finalize()
+            rows_fn = regenerated_rows(dump_seed, kind)
+            for call in range(3):
+                k = int(_pick(rng, [1, 10, 100, 200, 1024]))
+                n_q = min(int(rng.integers(1, 2101)), max(1, (1 << 18) // k))      # (the restatement's candidates: n_q x k x 768 float64)
+                nprobe = int(min(nlist, _pick(rng, [1, 16, 256, 1024, nlist])))
+                half = (n_q + 1) // 2
+                base = np.stack([synthetic_rows(int(r), 1, seed=dump_seed, kind=kind)[0] for r in rng.integers(0, n, half)])
+                x = np.concatenate([O.int8_to_float(base) + rng.normal(0, 0.25, (half, 768)),
+                                    rng.normal(0, 0.5, (n_q - half, 768))]).astype(np.float32)
+                where = f"{what} | call {call}: n_q {n_q} k {k} nprobe {nprobe}"
+                ref = gpu_ivf_flat_search_regenerated(x, cent, assign, rows_fn, n, nprobe, k)
+                check_ivf_calls(s, x, k, nprobe, nlist, ref, where)
+        finally:
+            s.close()
+            del s
+            gc.collect()
+            torch.cuda.empty_cache()

@@ -1096,3 +1096,58 @@ def test_buckets_beyond_the_sort_capacity_are_cut_to_their_best_keys_not_rescann
     ok, msg = O.topk_equivalent(D, I, D64, Ir)
     assert ok, msg
     np.testing.assert_array_equal(I[:8, 0], planted)
+
+
+@pytest.mark.gpu
+def test_boundary_ties_beyond_the_exact_scan_buffer_are_reported_never_answered():
+    """More exact ties at the k-th place than the fp64 scan's hit buffer (2^20 per row) holds: 2^20 + 2^16 copies of one row between
+    3000 + 3000 random rows (id_base 1000), and a query row for which every copy outscores every random row, in a batch with five
+    ordinary rows.  Pinned (include/dph.h, dph_search): the host form raises DPH_E_UNCERTIFIED and counts the row as uncertified; the
+    device form gives that row status 1 and answers the five others exactly with status 0.  No form may return success for the row
+    unless its ids are the k lowest ids of the tie set -- a silent wrong answer is the one outcome that must not happen."""
+    import torch
+    from densephrases_amd import Shard
+    from densephrases_amd._lib import DPH_E_UNCERTIFIED, DphError
+    from tests._devdata import gpu_flat_ip_search
+    from tests._fullsize import check_stats
+    rng = np.random.default_rng(66)
+    n_copy, id_base = (1 << 20) + (1 << 16), 1000
+    pattern = np.where(rng.random(768) < 0.5, 60, 20).astype(np.int8)            # de-quantised: +1 / -1
+    xb = np.concatenate([O.float_to_int8(rng.standard_normal((3000, 768), dtype=np.float32) * np.float32(0.6)),
+                         np.broadcast_to(pattern, (n_copy, 768)),
+                         O.float_to_int8(rng.standard_normal((3000, 768), dtype=np.float32) * np.float32(0.6))])
+    s = Shard(xb.shape[0], device=0, id_base=id_base)
+    s.upload(xb)
+    s.finalize()
+    c = O.int8_to_float(pattern).astype(np.float64)
+    x = np.zeros((6, 768), np.float32)
+    x[0] = c                                                                      # every copy scores 768, every random row far less
+    for r in range(1, 6):                                                         # near a random row, the copies well below it
+        v = O.int8_to_float(xb[int(rng.integers(0, 3000))]).astype(np.float64) + rng.normal(0, 0.1, 768)
+        x[r] = v - (v @ c + 200.0) / (c @ c) * c
+    ties = np.arange(3000, 3000 + n_copy) + id_base
+    dev = torch.device("cuda", 0)
+    for k in (10, 100):
+        with pytest.raises(DphError) as e:
+            D, I = s.search(x, k)
+            # (if it ever returns: the only acceptable answer for the tied row)
+            assert list(I[0]) == list(ties[:k]) and (D[0] == D[0, 0]).all(), (k, I[0][:8])
+        assert e.value.code == DPH_E_UNCERTIFIED, (k, e.value)
+        st = s.stats()
+        check_stats(st, len(x), f"k {k} host form")
+        assert st["uncertified"] == 1, (k, st)
+        xd = torch.from_numpy(x).to(dev)
+        Dd = torch.empty((len(x), k), dtype=torch.float32, device=dev)
+        Id = torch.empty((len(x), k), dtype=torch.int64, device=dev)
+        sd = torch.empty(len(x), dtype=torch.int32, device=dev)
+        s.search_dev(xd.data_ptr(), len(x), k, Dd.data_ptr(), Id.data_ptr(), sd.data_ptr())
+        torch.cuda.synchronize()
+        status, D, I = sd.cpu().numpy(), Dd.cpu().numpy(), Id.cpu().numpy()
+        st = s.stats()
+        check_stats(st, len(x), f"k {k} device form")
+        assert status[0] == 1 and (status[1:] == 0).all(), (k, status, st)
+        assert st["uncertified"] == 1, (k, st)
+        Dr, Ir, D64 = gpu_flat_ip_search(x[1:], xb, k, id_base=id_base)
+        np.testing.assert_array_equal(I[1:], Ir)
+        np.testing.assert_array_equal(D[1:], Dr)
+    s.close()

@@ -119,3 +119,51 @@ def test_mips_search_answers_the_other_queries_and_leaves_the_flagged_one_empty(
     for strat, sent in (("opt2", True), ("opt3", False), ("opt4", False)):
         kw2 = dict(top_k=5, aggregate=True, agg_strat=strat, return_sent=sent)
         assert list(mips.search_stream([q, q, q], q_texts=[list("abcdef")] * 3, **kw2)) == [mips.search(q, q_texts=list("abcdef"), **kw2)] * 3
+
+
+def test_stats_count_a_non_finite_row_once_on_every_index_type():
+    """dph_search_stats splits the rows of a call into certified_fast + certified_wide + exact_fallback + uncertified + nonfinite (a
+    non-finite row's stand-in is searched and certified like any row, but the row is counted as non-finite only), on a flat, an IVF
+    and a PQ handle, in the host form and in the device form (stats read after the call)."""
+    import torch
+    from densephrases_amd import Shard
+    from tests._fullsize import check_stats
+    from tests.test_ivf import _clustered_db, _ivf_shard
+    from tests.test_pq import _index_from_list_numbers, _shard
+    rng = np.random.default_rng(12)
+    xb, centres = _clustered_db(rng, 20000, 24)
+    flat = Shard(xb.shape[0], device=0, id_base=7)
+    flat.upload(xb)
+    flat.finalize()
+    ivf, _ = _ivf_shard(xb, centres[:16].astype(np.float32), units=-1)
+    nlist = 256
+    ix, _ = _index_from_list_numbers(rng, nlist, 64, rng.integers(0, nlist, 9000), rng.normal(0, 0.5, (nlist, 768)).astype(np.float32))
+    pq = _shard(ix)
+    x = rng.normal(0, 0.5, (9, 768)).astype(np.float32)
+    x[3, 11] = np.nan
+    x[6, :] = np.inf
+    dev = torch.device("cuda", 0)
+    xd = torch.from_numpy(x).to(dev)
+    k = 10
+    Dd = torch.empty((len(x), k), dtype=torch.float32, device=dev)
+    Id = torch.empty((len(x), k), dtype=torch.int64, device=dev)
+    sd = torch.empty(len(x), dtype=torch.int32, device=dev)
+    for name, s, host, devf in (("flat", flat, lambda: flat.search(x, k),
+                                 lambda: flat.search_dev(xd.data_ptr(), len(x), k, Dd.data_ptr(), Id.data_ptr(), sd.data_ptr())),
+                                ("ivf", ivf, lambda: ivf.search_ivf(x, k, 4),
+                                 lambda: ivf.search_ivf_dev(xd.data_ptr(), len(x), k, 4, Dd.data_ptr(), Id.data_ptr(), sd.data_ptr())),
+                                ("pq", pq, lambda: pq.search_ivf(x, k, 16),
+                                 lambda: pq.search_ivf_dev(xd.data_ptr(), len(x), k, 16, Dd.data_ptr(), Id.data_ptr(), sd.data_ptr()))):
+        D, I = host()
+        st = s.stats()
+        check_stats(st, len(x), f"{name} host form")
+        assert st["nonfinite"] == 2 and st["uncertified"] == 0, (name, st)
+        assert (I[[3, 6]] == -1).all() and (D[[3, 6]] == -FLT_MAX).all(), name
+        devf()
+        st = s.stats()                                     # (reads the device counters: synchronises)
+        check_stats(st, len(x), f"{name} device form")
+        assert st["nonfinite"] == 2 and st["uncertified"] == 0, (name, st)
+        status = sd.cpu().numpy()
+        assert (status[[3, 6]] == 3).all() and (np.delete(status, [3, 6]) == 0).all(), (name, status)
+        np.testing.assert_array_equal(Id.cpu().numpy(), I)
+        s.close()
