@@ -3,7 +3,57 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <string>
+#include <utility>
+#include <vector>
 #include "../../include/dph_debug.h"      // (includes dph.h: the contract + the tuning / profiling / debug entry points)
+
+// ---------------------------------------------------------------- errors and ownership (host side)
+// The one error channel: fail() stores the message dph_last_error() returns (thread-local, dph_api.hip) and hands the code back.
+int fail(int code, const std::string& msg);
+#define HIPCHK(expr)                                                                                 \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return fail(e_ == hipErrorOutOfMemory ? DPH_E_NOMEM : DPH_E_HIP,                         \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));                          \
+    } while (0)
+
+// Owner of one hipMalloc allocation of `n` elements.  Move-only; the destructor frees, so the struct a dev_buf is a member of releases
+// it wherever that struct dies (with its device current: dph_index_destroy / dph_pq_free).  Reads as a plain T* at the call sites.
+template <typename T> struct dev_buf {
+    T* p = nullptr;
+    size_t n = 0;
+    dev_buf() = default;
+    dev_buf(const dev_buf&) = delete;
+    dev_buf& operator=(const dev_buf&) = delete;
+    dev_buf(dev_buf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    dev_buf& operator=(dev_buf&& o) noexcept { if (this != &o) { reset(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+    ~dev_buf() { reset(); }
+    hipError_t alloc(size_t count) {     // frees what it held; on failure it holds nothing
+        reset();
+        const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        if (e == hipSuccess) n = count; else p = nullptr;
+        return e;
+    }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    operator T*() const { return p; }
+};
+
+// Owner of the (start, stop) event pairs that bracket profiled launches.
+struct dph_event_pairs {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> v;
+    dph_event_pairs() = default;
+    dph_event_pairs(const dph_event_pairs&) = delete;
+    dph_event_pairs& operator=(const dph_event_pairs&) = delete;
+    ~dph_event_pairs() { for (auto& ev : v) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); } }
+    std::pair<hipEvent_t, hipEvent_t> take() {           // a pair of this (free) list, or a new one when it is empty
+        std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+        if (!v.empty()) { ev = v.back(); v.pop_back(); }
+        else { (void)hipEventCreate(&ev.first); (void)hipEventCreate(&ev.second); }
+        return ev;
+    }
+};
 
 // ---------------------------------------------------------------- geometry of the scan
 // A scan workgroup is 4 waves, one per SIMD, one workgroup per CU.  Wave w owns QB groups of 32 query rows for the
@@ -320,7 +370,6 @@ void dph_launch_dense_logits(const float* s, const float* e, int64_t n_b, int64_
 
 // ---- the reference's own index type, IndexPreTransform(OPQMatrix) -> IndexIVFPQ, resident in HBM (dph_pq.hip)
 struct dph_pq;
-const char* dph_pq_error();
 int dph_pq_alloc(dph_pq** out, int device, int64_t ntotal, int nlist, int M);
 void dph_pq_free(dph_pq* p);
 int dph_pq_set_params(dph_pq* p, const float* A, const float* b, const float* centroids, const float* pq_centroids, int by_residual);

@@ -34,20 +34,6 @@
 #define PQ_SEG 12288                  // codes per segment (M <= 96: 96 KiB of LUT + 48 KiB of keys); halved for larger M (LDS budget).  12288: a row-major unit of the released shape (64 lists, ~10 k codes) is ONE segment -- one k-th selection per unit instead of two (8192: r1-r4)
 #define PQ_FINAL_CAP 4096             // candidates the final sort takes (k + boundary ties)
 
-static thread_local std::string g_pq_err;
-const char* dph_pq_error() { return g_pq_err.c_str(); }
-static int pq_fail(int code, const std::string& m) {
-    g_pq_err = m;
-    if (code == DPH_E_HIP || code == DPH_E_NOMEM) (void)hipGetLastError();       // (consumed: see fail() in dph_api.hip)
-    return code;
-}
-#define PQCHK(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return pq_fail(e_ == hipErrorOutOfMemory ? DPH_E_NOMEM : DPH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 __device__ __forceinline__ unsigned pq_key(float s) {
     const unsigned b = __float_as_uint(s);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);          // larger float <=> larger key; key 0 is below every score
@@ -883,68 +869,70 @@ __global__ __launch_bounds__(256) void pq_dup_kernel(const int64_t* sorted_ids, 
 void dph_pq_free(dph_pq* p);
 int dph_sort_pairs_i64_u32(const int64_t* keys_in, const unsigned* vals_in, int64_t* keys_out, unsigned* vals_out, int64_t n, hipStream_t st);
 
+// the per-pass scratch, sized by pq_ensure from (rows, k, nprobe) and the list lengths; released as a whole (`p->s = pq_scratch()`)
+struct pq_scratch {
+    int cap_rows = 0;
+    dev_buf<float> xp, lut, scores;
+    dev_buf<unsigned> xp_pk;                               // bf16 hi << 16 | lo of the rotated query rows of a pass
+    dev_buf<unsigned short> xp_hi;                         // ... and as plain bf16
+    dev_buf<unsigned> listmask;
+    dev_buf<int2> pairs; dev_buf<int> counters; dev_buf<uint2> cand;
+    unsigned *bound = nullptr, *cand_count = nullptr, *overflow = nullptr;   // (live behind `counters`)
+    int32_t* nf = nullptr;                                 // [rows] query rows with a NaN / Inf element (pq_transform_kernel; lives behind `counters`)
+    dev_buf<int> probe;                                    // [rows][nprobe] probed lists of every row (row-major scan)
+    dev_buf<int2> units;                                   // ... and its work queue: (group, segment) records (pq_units_kernel)
+};
+
 struct dph_pq {
     int device = 0, nlist = 0, M = 0, dsub = 0, by_residual = 1;
     int64_t ntotal = 0;
-    float *A = nullptr, *At = nullptr, *b = nullptr, *cent = nullptr, *pqc = nullptr;
-    unsigned* cent_pk = nullptr;                           // bf16 hi << 16 | lo of the centroids (long quantizers: the bf16x3 coarse GEMM)
-    unsigned* xp_pk = nullptr;                             // ... and of the rotated query rows of a pass (scratch)
-    unsigned short* cent_hi = nullptr;                     // the centroids as plain bf16: the coarse quantizer's one-product filter GEMM
-    unsigned short* cent_frag = nullptr;                   // ... once more in MFMA fragment order (filter GEMM variant 3)
-    unsigned short* cent_pieces = nullptr;                 // ... and as 24 KiB pieces with the byte layout of an int8 tile (the filter SCAN, variant 5)
-    unsigned short* xp_hi = nullptr;                       // ... and the rotated query rows of a pass (scratch)
-    void* coarse_cf = nullptr;                             // scratch of the filter form (dph_launch_coarse_filter)
+    dev_buf<float> A, At, b, cent, pqc;
+    dev_buf<unsigned> cent_pk;                             // bf16 hi << 16 | lo of the centroids (long quantizers: the bf16x3 coarse GEMM)
+    dev_buf<unsigned short> cent_hi;                       // the centroids as plain bf16: the coarse quantizer's one-product filter GEMM
+    dev_buf<unsigned short> cent_frag;                     // ... once more in MFMA fragment order (filter GEMM variant 3)
+    dev_buf<unsigned short> cent_pieces;                   // ... and as 24 KiB pieces with the byte layout of an int8 tile (the filter SCAN, variant 5)
     int split_lut = 0;                                     // tuning key "pq_split_lut": measured SLOWER (sums 148 us against 124 per workgroup), off
     int coarse_filter = 5;                                 // 0: the bf16x3 chain alone, 1 / 2: filter GEMM staging centroids and queries through LDS (2: centroid stream
                                                            // non-temporal), 3: centroids straight into registers from the fragment-major image, 4: 3 on contiguous tile runs,
                                                            // 5 (default, round 5): the filter as a SCAN -- bf16 centroid pieces through the flat scan's feed (dph_scan.hip MODE 3)
     int coarse_teams = 1;                                  // tuning key "coarse_teams": passes of more than 128 rows run the filter scan as ONE launch of workgroup teams
     bool profile = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events, prof_free;
+    dph_event_pairs prof_events, prof_free;
     std::vector<float> h_A;
-    uint8_t* codes = nullptr; int64_t* ids = nullptr; int64_t* list_off = nullptr;
+    dev_buf<uint8_t> codes; dev_buf<int64_t> ids, list_off;
     std::vector<int64_t> h_list_off;
-    int64_t* dm_ids = nullptr; unsigned* dm_pos = nullptr;
+    dev_buf<int64_t> dm_ids; dev_buf<unsigned> dm_pos;
     double cnorm_max = 0.0, cnorm_cap = 0.0;               // longest centroid; the length above which a list is HEAVY for the coarse filter (dph_coarse_select_kernel)
-    float* cnorm = nullptr;                                // [nlist] ||c_l||_2
+    dev_buf<float> cnorm;                                  // [nlist] ||c_l||_2
     int64_t max_list = 0;
     bool lists_set = false, params_set = false, finalized = false;
     // scratch, grown on demand
-    int cap_rows = 0, cap_k = 0, cap_nprobe = 0;
-    float *xp = nullptr, *lut = nullptr, *scores = nullptr, *qrot = nullptr;
-    unsigned *listmask = nullptr, *bound = nullptr, *cand_count = nullptr, *overflow = nullptr;
-    int2* pairs = nullptr; int* counters = nullptr; uint2* cand = nullptr; int cand_cap = 0; int pair_cap = 0;
-    int* probe = nullptr;                                  // [rows][nprobe] probed lists of every row (row-major scan)
-    int32_t* nf = nullptr;                                 // [rows] query rows with a NaN / Inf element (pq_transform_kernel; lives behind `counters`)
-    int2* units = nullptr; int unit_cap = 0;               // ... and its work queue: (group, segment) records (pq_units_kernel)
+    pq_scratch s;
+    int cap_k = 0, cap_nprobe = 0, cand_cap = 0, pair_cap = 0, unit_cap = 0;
     std::vector<int64_t> h_top_prefix;                     // [i] = codes in the i longest lists: what a row can meet at most with nprobe = i
-    int64_t qrot_rows = 0;
-    void* coarse_cs = nullptr;                             // candidate scratch of the one-pass probe selection (dph_launch_coarse_presplit)
-    unsigned long long* phase_prof = nullptr;              // dph_debug_pq_phases: [workgroups][8], allocated by the first call
+    // what lives until the index is freed
+    dev_buf<float> qrot; int64_t qrot_rows = 0;            // rotated query halves of dph_pq_window
+    void* coarse_cs = nullptr;                             // candidate scratch of the one-pass probe selection (allocated by dph_launch_coarse_presplit)
+    void* coarse_cf = nullptr;                             // scratch of the filter form (allocated by dph_launch_coarse_filter)
+    dev_buf<unsigned long long> phase_prof;                // dph_debug_pq_phases: [workgroups][8], allocated by the first call
     int phase_wgs = 0;
+    ~dph_pq() { if (coarse_cs) (void)hipFree(coarse_cs); if (coarse_cf) (void)hipFree(coarse_cf); }
 };
-
-static void pq_free_scratch(dph_pq* p) {
-    void* v[] = {p->xp, p->lut, p->scores, p->listmask, p->pairs, p->counters, p->cand, p->probe, p->xp_pk, p->xp_hi, p->units};      // (bound / cand_count / overflow live behind counters)
-    for (void* q : v) if (q) (void)hipFree(q);
-    p->xp = p->lut = p->scores = nullptr; p->listmask = p->bound = p->cand_count = p->overflow = nullptr; p->nf = nullptr;
-    p->pairs = nullptr; p->counters = nullptr; p->cand = nullptr; p->probe = nullptr; p->xp_pk = nullptr; p->xp_hi = nullptr; p->units = nullptr; p->cap_rows = 0;
-}
 
 int dph_pq_alloc(dph_pq** out, int device, int64_t ntotal, int nlist, int M) {
     if (!out || ntotal < 0 || nlist <= 0 || nlist > (1 << 20) || M <= 0 || DPH_DIM % M || M % 16 || M > 128)
-        return pq_fail(DPH_E_ARG, "PQ index: need 0 < nlist <= 2^20 and M a multiple of 16 that divides 768, M <= 128");
-    if (ntotal >= (int64_t)0xFFFFFFF0ll) return pq_fail(DPH_E_ARG, "PQ index: at most 2^32-16 codes per GPU");
-    PQCHK(hipSetDevice(device));
+        return fail(DPH_E_ARG, "PQ index: need 0 < nlist <= 2^20 and M a multiple of 16 that divides 768, M <= 128");
+    if (ntotal >= (int64_t)0xFFFFFFF0ll) return fail(DPH_E_ARG, "PQ index: at most 2^32-16 codes per GPU");
+    HIPCHK(hipSetDevice(device));
     dph_pq* p = new dph_pq();
     p->device = device; p->ntotal = ntotal; p->nlist = nlist; p->M = M; p->dsub = DPH_DIM / M;
     const size_t nt = (size_t)(ntotal > 0 ? ntotal : 1);
-    if (hipMalloc((void**)&p->cent, (size_t)nlist * DPH_DIM * 4) != hipSuccess || hipMalloc((void**)&p->pqc, (size_t)256 * DPH_DIM * 4) != hipSuccess ||
-        hipMalloc((void**)&p->codes, nt * M + 16) != hipSuccess || hipMalloc((void**)&p->ids, nt * 8) != hipSuccess ||
-        hipMalloc((void**)&p->list_off, ((size_t)nlist + 1) * 8) != hipSuccess || hipMalloc((void**)&p->dm_ids, nt * 8) != hipSuccess ||
-        hipMalloc((void**)&p->dm_pos, nt * 4) != hipSuccess) {
+    if (p->cent.alloc((size_t)nlist * DPH_DIM) != hipSuccess || p->pqc.alloc((size_t)256 * DPH_DIM) != hipSuccess ||
+        p->codes.alloc(nt * M + 16) != hipSuccess || p->ids.alloc(nt) != hipSuccess ||
+        p->list_off.alloc((size_t)nlist + 1) != hipSuccess || p->dm_ids.alloc(nt) != hipSuccess ||
+        p->dm_pos.alloc(nt) != hipSuccess) {
         dph_pq_free(p);
-        return pq_fail(DPH_E_NOMEM, "PQ index: hipMalloc failed");
+        return fail(DPH_E_NOMEM, "PQ index: hipMalloc failed");
     }
     *out = p;
     return DPH_OK;
@@ -954,34 +942,34 @@ void dph_pq_set_split_lut(dph_pq* p, int on) { if (p) p->split_lut = on ? 1 : 0;
 void dph_pq_set_coarse_filter(dph_pq* p, int on) { if (p) p->coarse_filter = on < 0 ? 0 : (on > 5 ? 5 : on); }
 void dph_pq_set_coarse_teams(dph_pq* p, int on) { if (p) p->coarse_teams = on ? 1 : 0; }
 int dph_pq_coarse_debug(dph_pq* p, unsigned out[2]) {
-    if (!p) return pq_fail(DPH_E_ARG, "null");
-    PQCHK(hipSetDevice(p->device));
-    PQCHK(hipDeviceSynchronize());
-    return dph_coarse_filter_debug(p->coarse_cf, out) ? pq_fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
+    if (!p) return fail(DPH_E_ARG, "null");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());
+    return dph_coarse_filter_debug(p->coarse_cf, out) ? fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
 }
 int dph_pq_coarse_debug_pool(dph_pq* p, unsigned* lk_host, unsigned short* q_host, long long cap, long long* count) {
-    if (!p || !count) return pq_fail(DPH_E_ARG, "null");
-    PQCHK(hipSetDevice(p->device));
-    PQCHK(hipDeviceSynchronize());
+    if (!p || !count) return fail(DPH_E_ARG, "null");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());
     *count = dph_coarse_filter_debug_pool(p->coarse_cf, lk_host, q_host, cap);
-    return *count < 0 ? pq_fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
+    return *count < 0 ? fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
 }
 // what the LAST pass left in the scan's bookkeeping: info[8] = {counters[0..3] (pairs, next, units, -), cand_cap, unit_cap, pair_cap, rows of
 // the scratch}, per_row[n][3] = {appended candidates, overflow flag, bound key} of the first n rows.  (tests/test_fuzz_gpu.py prints it
 // for a round that comes back uncertified.)
 int dph_pq_debug_pass(dph_pq* p, int* info, unsigned* per_row, int n) {
-    if (!p || !info || n < 0) return pq_fail(DPH_E_ARG, "null");
-    if (!p->counters) return pq_fail(DPH_E_STATE, "PQ debug: no search yet");
-    PQCHK(hipSetDevice(p->device));
-    PQCHK(hipDeviceSynchronize());
-    PQCHK(hipMemcpy(info, p->counters, 16, hipMemcpyDeviceToHost));
-    info[4] = p->cand_cap; info[5] = p->unit_cap; info[6] = p->pair_cap; info[7] = p->cap_rows;
-    n = std::min(n, p->cap_rows);
+    if (!p || !info || n < 0) return fail(DPH_E_ARG, "null");
+    if (!p->s.counters) return fail(DPH_E_STATE, "PQ debug: no search yet");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(info, p->s.counters, 16, hipMemcpyDeviceToHost));
+    info[4] = p->cand_cap; info[5] = p->unit_cap; info[6] = p->pair_cap; info[7] = p->s.cap_rows;
+    n = std::min(n, p->s.cap_rows);
     std::vector<unsigned> a((size_t)n), b((size_t)n), c((size_t)n);
     if (n > 0 && per_row) {
-        PQCHK(hipMemcpy(a.data(), p->cand_count, (size_t)n * 4, hipMemcpyDeviceToHost));
-        PQCHK(hipMemcpy(b.data(), p->overflow, (size_t)n * 4, hipMemcpyDeviceToHost));
-        PQCHK(hipMemcpy(c.data(), p->bound, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(a.data(), p->s.cand_count, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b.data(), p->s.overflow, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c.data(), p->s.bound, (size_t)n * 4, hipMemcpyDeviceToHost));
         for (int r = 0; r < n; ++r) { per_row[3 * r] = a[(size_t)r]; per_row[3 * r + 1] = b[(size_t)r]; per_row[3 * r + 2] = c[(size_t)r]; }
     }
     return DPH_OK;
@@ -996,7 +984,7 @@ int dph_pq_debug_phases(dph_pq* p, int which, unsigned long long* out, int cap_w
     if (!p->phase_prof) {
         int cus = 256;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
-        if (hipMalloc((void**)&p->phase_prof, (size_t)cus * 64) != hipSuccess) { p->phase_prof = nullptr; return -1; }
+        if (p->phase_prof.alloc((size_t)cus * 8) != hipSuccess) return -1;
         (void)hipMemset(p->phase_prof, 0, (size_t)cus * 64);
         p->phase_wgs = cus;
     }
@@ -1005,49 +993,49 @@ int dph_pq_debug_phases(dph_pq* p, int which, unsigned long long* out, int cap_w
     return p->phase_wgs;
 }
 int dph_pq_profile(dph_pq* p, int on) {
-    if (!p) return pq_fail(DPH_E_ARG, "null");
-    PQCHK(hipSetDevice(p->device));
+    if (!p) return fail(DPH_E_ARG, "null");
+    HIPCHK(hipSetDevice(p->device));
     p->profile = on != 0;
-    while (p->profile && p->prof_free.size() < 64) {
+    while (p->profile && p->prof_free.v.size() < 64) {
         std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-        PQCHK(hipEventCreate(&ev.first));
-        PQCHK(hipEventCreate(&ev.second));
-        p->prof_free.push_back(ev);
+        HIPCHK(hipEventCreate(&ev.first));
+        HIPCHK(hipEventCreate(&ev.second));
+        p->prof_free.v.push_back(ev);
     }
     return DPH_OK;
 }
 int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches) {
-    if (!p || !ms_total || !launches) return pq_fail(DPH_E_ARG, "null");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || !ms_total || !launches) return fail(DPH_E_ARG, "null");
+    HIPCHK(hipSetDevice(p->device));
     double total = 0.0;
     int cnt = 0;
-    for (auto& ev : p->prof_events) {
-        PQCHK(hipEventSynchronize(ev.second));
+    for (auto& ev : p->prof_events.v) {
+        HIPCHK(hipEventSynchronize(ev.second));
         float ms = 0.f;
-        PQCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
+        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
         total += ms;
         ++cnt;
-        p->prof_free.push_back(ev);
+        p->prof_free.v.push_back(ev);
     }
-    p->prof_events.clear();
+    p->prof_events.v.clear();
     *ms_total = total;
     *launches = cnt;
     return DPH_OK;
 }
 
 int dph_pq_profile_read_each(dph_pq* p, double* ms_out, int cap, int* n_out) {
-    if (!p || !n_out) return pq_fail(DPH_E_ARG, "null");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || !n_out) return fail(DPH_E_ARG, "null");
+    HIPCHK(hipSetDevice(p->device));
     int n = 0;
-    for (auto& ev : p->prof_events) {
-        PQCHK(hipEventSynchronize(ev.second));
+    for (auto& ev : p->prof_events.v) {
+        HIPCHK(hipEventSynchronize(ev.second));
         float ms = 0.f;
-        PQCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
+        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
         if (n < cap && ms_out) ms_out[n] = ms;
         ++n;
-        p->prof_free.push_back(ev);
+        p->prof_free.v.push_back(ev);
     }
-    p->prof_events.clear();
+    p->prof_events.v.clear();
     *n_out = n;
     return DPH_OK;
 }
@@ -1055,48 +1043,41 @@ int dph_pq_profile_read_each(dph_pq* p, double* ms_out, int cap, int* n_out) {
 void dph_pq_free(dph_pq* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    for (auto& ev : p->prof_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    for (auto& ev : p->prof_free) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    pq_free_scratch(p);
-    void* v[] = {p->A, p->At, p->b, p->cent, p->pqc, p->codes, p->ids, p->list_off, p->dm_ids, p->dm_pos, p->qrot, p->cent_pk, p->coarse_cs, p->cent_hi, p->coarse_cf, p->cent_frag, p->cent_pieces, p->phase_prof, p->cnorm};
-    for (void* q : v) if (q) (void)hipFree(q);
     delete p;
 }
 
 int dph_pq_set_params(dph_pq* p, const float* A, const float* b, const float* centroids, const float* pq_centroids, int by_residual) {
-    if (!p || !centroids || !pq_centroids) return pq_fail(DPH_E_ARG, "PQ index: null parameter");
-    PQCHK(hipSetDevice(p->device));
-    if (p->A) { (void)hipFree(p->A); p->A = nullptr; }
-    if (p->At) { (void)hipFree(p->At); p->At = nullptr; }
-    if (p->b) { (void)hipFree(p->b); p->b = nullptr; }
+    if (!p || !centroids || !pq_centroids) return fail(DPH_E_ARG, "PQ index: null parameter");
+    HIPCHK(hipSetDevice(p->device));
+    p->A.reset(); p->At.reset(); p->b.reset();
     p->h_A.assign((size_t)DPH_DIM * DPH_DIM, 0.f);
     if (A) {
         p->h_A.assign(A, A + (size_t)DPH_DIM * DPH_DIM);
         std::vector<float> At((size_t)DPH_DIM * DPH_DIM);
         for (int i = 0; i < DPH_DIM; ++i) for (int j = 0; j < DPH_DIM; ++j) At[(size_t)j * DPH_DIM + i] = A[(size_t)i * DPH_DIM + j];
-        PQCHK(hipMalloc((void**)&p->A, At.size() * 4));
-        PQCHK(hipMalloc((void**)&p->At, At.size() * 4));
-        PQCHK(hipMemcpy(p->A, A, At.size() * 4, hipMemcpyHostToDevice));
-        PQCHK(hipMemcpy(p->At, At.data(), At.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(p->A.alloc(At.size()));
+        HIPCHK(p->At.alloc(At.size()));
+        HIPCHK(hipMemcpy(p->A, A, At.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->At, At.data(), At.size() * 4, hipMemcpyHostToDevice));
     } else {
         for (int i = 0; i < DPH_DIM; ++i) p->h_A[(size_t)i * DPH_DIM + i] = 1.f;
     }
     if (b) {
-        PQCHK(hipMalloc((void**)&p->b, DPH_DIM * 4));
-        PQCHK(hipMemcpy(p->b, b, DPH_DIM * 4, hipMemcpyHostToDevice));
+        HIPCHK(p->b.alloc(DPH_DIM));
+        HIPCHK(hipMemcpy(p->b, b, DPH_DIM * 4, hipMemcpyHostToDevice));
     }
-    PQCHK(hipMemcpy(p->cent, centroids, (size_t)p->nlist * DPH_DIM * 4, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(p->pqc, pq_centroids, (size_t)256 * DPH_DIM * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->cent, centroids, (size_t)p->nlist * DPH_DIM * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->pqc, pq_centroids, (size_t)256 * DPH_DIM * 4, hipMemcpyHostToDevice));
     if (p->nlist >= (1 << 16)) {                    // CG_BF16X3_MIN of dph_ivf.hip: the coarse GEMM of long quantizers runs on bf16 hi / lo parts
-        if (!p->cent_pk) PQCHK(hipMalloc((void**)&p->cent_pk, (size_t)p->nlist * DPH_DIM * 4));
+        if (!p->cent_pk) HIPCHK(p->cent_pk.alloc((size_t)p->nlist * DPH_DIM));
         dph_launch_bf16_split(p->cent, (int64_t)p->nlist * DPH_DIM, p->cent_pk, nullptr);
-        if (!p->cent_hi) PQCHK(hipMalloc((void**)&p->cent_hi, (size_t)dph_bf16_hi_rows(p->nlist, 1) * DPH_DIM * 2));
+        if (!p->cent_hi) HIPCHK(p->cent_hi.alloc((size_t)dph_bf16_hi_rows(p->nlist, 1) * DPH_DIM));
         dph_launch_bf16_hi(p->cent, p->nlist, 1, p->cent_hi, nullptr);
-        if (!p->cent_frag) PQCHK(hipMalloc((void**)&p->cent_frag, (size_t)dph_bf16_frag_rows(p->nlist) * DPH_DIM * 2));
+        if (!p->cent_frag) HIPCHK(p->cent_frag.alloc((size_t)dph_bf16_frag_rows(p->nlist) * DPH_DIM));
         dph_launch_bf16_frag(p->cent, p->nlist, p->cent_frag, nullptr);
-        if (!p->cent_pieces) PQCHK(hipMalloc((void**)&p->cent_pieces, (size_t)dph_bf16_piece_rows(p->nlist) * DPH_DIM * 2));
+        if (!p->cent_pieces) HIPCHK(p->cent_pieces.alloc((size_t)dph_bf16_piece_rows(p->nlist) * DPH_DIM));
         dph_launch_bf16_pieces(p->cent, p->nlist, p->cent_pieces, nullptr);
-        PQCHK(hipDeviceSynchronize());
+        HIPCHK(hipDeviceSynchronize());
     }
     double mx = 0.0;
     std::vector<float> cn((size_t)p->nlist);
@@ -1113,8 +1094,8 @@ int dph_pq_set_params(dph_pq* p, const float* A, const float* b, const float* ce
         const size_t q99 = (size_t)((double)(p->nlist - 1) * 0.99);
         std::nth_element(srt.begin(), srt.begin() + (std::ptrdiff_t)q99, srt.end());
         p->cnorm_cap = std::min(p->cnorm_max, 1.1 * (double)srt[q99]);
-        if (!p->cnorm) PQCHK(hipMalloc((void**)&p->cnorm, (size_t)p->nlist * 4));
-        PQCHK(hipMemcpy(p->cnorm, cn.data(), (size_t)p->nlist * 4, hipMemcpyHostToDevice));
+        if (!p->cnorm) HIPCHK(p->cnorm.alloc((size_t)p->nlist));
+        HIPCHK(hipMemcpy(p->cnorm, cn.data(), (size_t)p->nlist * 4, hipMemcpyHostToDevice));
     }
     p->by_residual = by_residual ? 1 : 0;
     p->params_set = true;
@@ -1122,48 +1103,48 @@ int dph_pq_set_params(dph_pq* p, const float* A, const float* b, const float* ce
 }
 
 int dph_pq_set_list_sizes(dph_pq* p, const int64_t* sizes) {
-    if (!p || !sizes) return pq_fail(DPH_E_ARG, "PQ index: null list sizes");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || !sizes) return fail(DPH_E_ARG, "PQ index: null list sizes");
+    HIPCHK(hipSetDevice(p->device));
     p->h_list_off.assign((size_t)p->nlist + 1, 0);
     p->max_list = 0;
     for (int l = 0; l < p->nlist; ++l) {
-        if (sizes[l] < 0) return pq_fail(DPH_E_ARG, "PQ index: negative list size");
+        if (sizes[l] < 0) return fail(DPH_E_ARG, "PQ index: negative list size");
         p->h_list_off[(size_t)l + 1] = p->h_list_off[(size_t)l] + sizes[l];
         p->max_list = std::max(p->max_list, sizes[l]);
     }
-    if (p->h_list_off[(size_t)p->nlist] != p->ntotal) return pq_fail(DPH_E_ARG, "PQ index: list sizes do not add up to ntotal");
-    PQCHK(hipMemcpy(p->list_off, p->h_list_off.data(), ((size_t)p->nlist + 1) * 8, hipMemcpyHostToDevice));
+    if (p->h_list_off[(size_t)p->nlist] != p->ntotal) return fail(DPH_E_ARG, "PQ index: list sizes do not add up to ntotal");
+    HIPCHK(hipMemcpy(p->list_off, p->h_list_off.data(), ((size_t)p->nlist + 1) * 8, hipMemcpyHostToDevice));
     {
         std::vector<int64_t> srt(sizes, sizes + p->nlist);
         std::sort(srt.begin(), srt.end(), [](int64_t x, int64_t y) { return x > y; });
         p->h_top_prefix.assign((size_t)p->nlist + 1, 0);
         for (int l = 0; l < p->nlist; ++l) p->h_top_prefix[(size_t)l + 1] = p->h_top_prefix[(size_t)l] + srt[(size_t)l];
     }
-    pq_free_scratch(p);                                    // (the scratch is sized from the list lengths)
+    p->s = pq_scratch();                                   // (the scratch is sized from the list lengths)
     p->lists_set = true;
     p->finalized = false;
     return DPH_OK;
 }
 
 int dph_pq_upload(dph_pq* p, int64_t pos0, int64_t n, const uint8_t* codes, const int64_t* ids) {
-    if (!p || n < 0 || pos0 < 0 || pos0 + n > p->ntotal || (n > 0 && (!codes || !ids))) return pq_fail(DPH_E_ARG, "PQ index: bad code range");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || n < 0 || pos0 < 0 || pos0 + n > p->ntotal || (n > 0 && (!codes || !ids))) return fail(DPH_E_ARG, "PQ index: bad code range");
+    HIPCHK(hipSetDevice(p->device));
     if (n > 0) {
-        PQCHK(hipMemcpy(p->codes + (size_t)pos0 * p->M, codes, (size_t)n * p->M, hipMemcpyHostToDevice));
-        PQCHK(hipMemcpy(p->ids + pos0, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->codes + (size_t)pos0 * p->M, codes, (size_t)n * p->M, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->ids + pos0, ids, (size_t)n * 8, hipMemcpyHostToDevice));
     }
     p->finalized = false;
     return DPH_OK;
 }
 
 int dph_pq_finalize(dph_pq* p, hipStream_t st) {
-    if (!p || !p->params_set || !p->lists_set) return pq_fail(DPH_E_STATE, "PQ index: parameters / list sizes not set");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || !p->params_set || !p->lists_set) return fail(DPH_E_STATE, "PQ index: parameters / list sizes not set");
+    HIPCHK(hipSetDevice(p->device));
     if (p->ntotal > 0) {
-        unsigned* iota = nullptr;
-        int* dup = nullptr;
-        PQCHK(hipMalloc((void**)&iota, (size_t)p->ntotal * 4));
-        if (hipMalloc((void**)&dup, 4) != hipSuccess) { (void)hipFree(iota); return pq_fail(DPH_E_NOMEM, "PQ index: hipMalloc"); }
+        dev_buf<unsigned> iota;
+        dev_buf<int> dup;
+        HIPCHK(iota.alloc((size_t)p->ntotal));
+        if (dup.alloc(1) != hipSuccess) return fail(DPH_E_NOMEM, "PQ index: hipMalloc");
         (void)hipMemsetAsync(dup, 0, 4, st);
         hipLaunchKernelGGL(pq_iota_kernel, dim3((unsigned)((p->ntotal + 255) / 256)), dim3(256), 0, st, iota, p->ntotal);
         int rc = dph_sort_pairs_i64_u32(p->ids, iota, p->dm_ids, p->dm_pos, p->ntotal, st);
@@ -1172,9 +1153,8 @@ int dph_pq_finalize(dph_pq* p, hipStream_t st) {
             hipLaunchKernelGGL(pq_dup_kernel, dim3((unsigned)((p->ntotal + 255) / 256)), dim3(256), 0, st, p->dm_ids, p->ntotal, dup);
             if (hipMemcpyAsync(&dup_h, dup, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = 1;
         }
-        (void)hipFree(iota); (void)hipFree(dup);
-        if (rc) return pq_fail(DPH_E_HIP, "PQ index: building the direct map failed");
-        if (dup_h) return pq_fail(DPH_E_ARG, "PQ index: duplicate ids in the inverted lists");
+        if (rc) return fail(DPH_E_HIP, "PQ index: building the direct map failed");
+        if (dup_h) return fail(DPH_E_ARG, "PQ index: duplicate ids in the inverted lists");
     }
     p->finalized = true;
     return DPH_OK;
@@ -1198,9 +1178,9 @@ static int64_t pq_row_units_max(const dph_pq* p, int nprobe) {
 static size_t pq_lds_bytes(const dph_pq* p) { return (size_t)p->M * 1024 + (size_t)pq_seg(p) * 4 + 264 * 4 + 16 * 8 + 16; }
 
 static int pq_ensure(dph_pq* p, int rows, int k, int nprobe) {
-    if (rows <= p->cap_rows && k <= p->cap_k && nprobe <= p->cap_nprobe) return DPH_OK;
-    rows = std::max(rows, p->cap_rows); k = std::max(k, p->cap_k); nprobe = std::max(nprobe, p->cap_nprobe);
-    pq_free_scratch(p);
+    if (rows <= p->s.cap_rows && k <= p->cap_k && nprobe <= p->cap_nprobe) return DPH_OK;
+    rows = std::max(rows, p->s.cap_rows); k = std::max(k, p->cap_k); nprobe = std::max(nprobe, p->cap_nprobe);
+    p->s = pq_scratch();
     // every segment may append its k best -- or, in the row-major scan (pq_segment_finish<true>: the bound of a long segment is the k-th of
     // a 1024-key sample), about k * seg / 1024 keys: twice that is reserved
     const bool by_rows = pq_by_rows(p);
@@ -1219,30 +1199,30 @@ static int pq_ensure(dph_pq* p, int rows, int k, int nprobe) {
     // list-major pairs: one per chunk of PQ_LM_CHUNK segments of a probed list -- at most nprobe + (codes of the nprobe longest lists) / chunk per row
     p->pair_cap = (int)std::min<int64_t>((int64_t)rows * (nprobe + (by_rows ? 0 : (p->h_top_prefix.empty() ? p->ntotal : p->h_top_prefix[(size_t)std::min(nprobe, p->nlist)]) / ((int64_t)pq_seg(p) * PQ_LM_CHUNK))), 1 << 28);
     p->unit_cap = by_rows ? (int)std::min<int64_t>((int64_t)rows * pq_row_units_max(p, nprobe), 1 << 28) : 0;
-    if (hipMalloc((void**)&p->xp, (size_t)rows * DPH_DIM * 4) != hipSuccess || hipMalloc((void**)&p->lut, (size_t)rows * p->M * 1024) != hipSuccess ||
-        hipMalloc((void**)&p->scores, (size_t)rows * p->nlist * 4) != hipSuccess || hipMalloc((void**)&p->listmask, (size_t)p->nlist * DPH_UNIT_WORDS * 4) != hipSuccess ||
-        hipMalloc((void**)&p->counters, 64 + (size_t)4 * rows * 4) != hipSuccess ||        // counters | bound | cand_count | overflow (one memset per pass) | non-finite flags
-        hipMalloc((void**)&p->pairs, (size_t)p->pair_cap * 8) != hipSuccess ||
-        hipMalloc((void**)&p->cand, (size_t)rows * p->cand_cap * 8) != hipSuccess ||
-        hipMalloc((void**)&p->probe, (size_t)rows * nprobe * 4) != hipSuccess ||
-        (p->unit_cap > 0 && hipMalloc((void**)&p->units, (size_t)p->unit_cap * 8) != hipSuccess) ||
-        hipMalloc((void**)&p->xp_pk, (size_t)rows * DPH_DIM * 4) != hipSuccess ||
-        hipMalloc((void**)&p->xp_hi, (size_t)rows * DPH_DIM * 2) != hipSuccess) {
-        pq_free_scratch(p);
-        return pq_fail(DPH_E_NOMEM, "PQ search: scratch allocation failed");
+    if (p->s.xp.alloc((size_t)rows * DPH_DIM) != hipSuccess || p->s.lut.alloc((size_t)rows * p->M * 256) != hipSuccess ||
+        p->s.scores.alloc((size_t)rows * p->nlist) != hipSuccess || p->s.listmask.alloc((size_t)p->nlist * DPH_UNIT_WORDS) != hipSuccess ||
+        p->s.counters.alloc(16 + (size_t)4 * rows) != hipSuccess ||        // counters | bound | cand_count | overflow (one memset per pass) | non-finite flags
+        p->s.pairs.alloc((size_t)p->pair_cap) != hipSuccess ||
+        p->s.cand.alloc((size_t)rows * p->cand_cap) != hipSuccess ||
+        p->s.probe.alloc((size_t)rows * nprobe) != hipSuccess ||
+        (p->unit_cap > 0 && p->s.units.alloc((size_t)p->unit_cap) != hipSuccess) ||
+        p->s.xp_pk.alloc((size_t)rows * DPH_DIM) != hipSuccess ||
+        p->s.xp_hi.alloc((size_t)rows * DPH_DIM) != hipSuccess) {
+        p->s = pq_scratch();
+        return fail(DPH_E_NOMEM, "PQ search: scratch allocation failed");
     }
-    p->bound = (unsigned*)(p->counters + 16);
-    p->cand_count = p->bound + rows;
-    p->overflow = p->cand_count + rows;
-    p->nf = (int32_t*)(p->overflow + rows);
-    p->cap_rows = rows; p->cap_k = k; p->cap_nprobe = nprobe;
+    p->s.bound = (unsigned*)(p->s.counters + 16);
+    p->s.cand_count = p->s.bound + rows;
+    p->s.overflow = p->s.cand_count + rows;
+    p->s.nf = (int32_t*)(p->s.overflow + rows);
+    p->s.cap_rows = rows; p->cap_k = k; p->cap_nprobe = nprobe;
     return DPH_OK;
 }
 
 // x_dev [n,768] -> D/I [n,k], status [n] (0 = exact top-k of the probed lists, 1 = candidate buffers overflowed); asynchronous on st
 int dph_pq_search_dev(dph_pq* p, const float* x_dev, int64_t n, int k, int nprobe, float* D, int64_t* I, int32_t* status, hipStream_t st) {
-    if (!p || !p->finalized) return pq_fail(DPH_E_STATE, "PQ search: index not finalized");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ search: index not finalized");
+    HIPCHK(hipSetDevice(p->device));
     nprobe = std::max(1, std::min(nprobe, p->nlist));
     const int pass = (int)std::min<int64_t>(n, DPH_PASS_MAX);
     int rc = pq_ensure(p, pass, k, nprobe);
@@ -1252,27 +1232,27 @@ int dph_pq_search_dev(dph_pq* p, const float* x_dev, int64_t n, int k, int nprob
         hipError_t e = hipSuccess;
         const void* ks[4] = {(const void*)pq_adc_kernel<6>, (const void*)pq_adc_kernel<8>, (const void*)pq_adc_rows_kernel<6>, (const void*)pq_adc_rows_kernel<8>};
         for (const void* kf : ks) if (e == hipSuccess) e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pq_lds_bytes(p));
-        if (e != hipSuccess) return pq_fail(DPH_E_HIP, std::string("PQ search: hipFuncSetAttribute: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(DPH_E_HIP, std::string("PQ search: hipFuncSetAttribute: ") + hipGetErrorString(e));
         if (p->device < 64) attr_bytes[p->device] = pq_lds_bytes(p);
     }
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
     for (int64_t q0 = 0; q0 < n; q0 += DPH_PASS_MAX) {
         const int nq = (int)std::min<int64_t>(n - q0, DPH_PASS_MAX);
-        if (pq_launch_transform(x_dev + q0 * DPH_DIM, p->At, nq, p->b, p->xp, p->cent_pk ? p->xp_hi : (unsigned short*)nullptr, p->cent_pk ? p->xp_pk : (unsigned*)nullptr, p->device, st, p->nf))
-            return pq_fail(DPH_E_HIP, "PQ search: hipFuncSetAttribute(pq_transform_kernel)");
+        if (pq_launch_transform(x_dev + q0 * DPH_DIM, p->At, nq, p->b, p->s.xp, p->cent_pk ? p->s.xp_hi : (unsigned short*)nullptr, p->cent_pk ? p->s.xp_pk : (unsigned*)nullptr, p->device, st, p->s.nf))
+            return fail(DPH_E_HIP, "PQ search: hipFuncSetAttribute(pq_transform_kernel)");
         {
             const dim3 lg(nq, (p->M + 7) / 8);
-            if (p->dsub == 8) hipLaunchKernelGGL(pq_lut_kernel<8>, lg, dim3(256), 0, st, p->xp, p->pqc, p->M, p->dsub, p->lut);             // M = 96 (the released OPQ96)
-            else if (p->dsub == 12) hipLaunchKernelGGL(pq_lut_kernel<12>, lg, dim3(256), 0, st, p->xp, p->pqc, p->M, p->dsub, p->lut);       // M = 64
-            else if (p->dsub == 16) hipLaunchKernelGGL(pq_lut_kernel<16>, lg, dim3(256), 0, st, p->xp, p->pqc, p->M, p->dsub, p->lut);       // M = 48
-            else hipLaunchKernelGGL(pq_lut_kernel<0>, lg, dim3(256), 0, st, p->xp, p->pqc, p->M, p->dsub, p->lut);
+            if (p->dsub == 8) hipLaunchKernelGGL(pq_lut_kernel<8>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);             // M = 96 (the released OPQ96)
+            else if (p->dsub == 12) hipLaunchKernelGGL(pq_lut_kernel<12>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);       // M = 64
+            else if (p->dsub == 16) hipLaunchKernelGGL(pq_lut_kernel<16>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);       // M = 48
+            else hipLaunchKernelGGL(pq_lut_kernel<0>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);
         }
         // many short lists on average: group the work by query row, cut by code count (pq_units_kernel)
         const bool by_rows = pq_by_rows(p);
-        PQCHK(hipMemsetAsync(p->counters, 0, 64 + (size_t)3 * p->cap_rows * 4, st));      // counters, bounds, candidate counts, overflow flags (the coarse
+        HIPCHK(hipMemsetAsync(p->s.counters, 0, 64 + (size_t)3 * p->s.cap_rows * 4, st));      // counters, bounds, candidate counts, overflow flags (the coarse
                                                                                           // quantizer flags a row whose error band overflows there too)
-        unsigned* const lmask = by_rows ? nullptr : p->listmask;       // the row-major scan walks the probe lists, not the masks (134 MB to clear at 2^20 lists)
+        unsigned* const lmask = by_rows ? nullptr : p->s.listmask;       // the row-major scan walks the probe lists, not the masks (134 MB to clear at 2^20 lists)
         if (p->cent_hi && p->coarse_filter) {
             // profiling: an event pair of its own around EVERY launch of the filter's dominant kernel (the scan; the GEMM forms: the one
             // GEMM launch) -- what a rocprofv3 kernel trace reports per dispatch, so the two can be held against each other
@@ -1281,54 +1261,52 @@ int dph_pq_search_dev(dph_pq* p, const float* x_dev, int64_t n, int k, int nprob
                 src.ctx = p;
                 src.next = [](void* ctx, hipEvent_t* a, hipEvent_t* b) {
                     dph_pq* q = (dph_pq*)ctx;
-                    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-                    if (!q->prof_free.empty()) { ev = q->prof_free.back(); q->prof_free.pop_back(); }
-                    else { (void)hipEventCreate(&ev.first); (void)hipEventCreate(&ev.second); }
-                    q->prof_events.push_back(ev);
+                    const std::pair<hipEvent_t, hipEvent_t> ev = q->prof_free.take();
+                    q->prof_events.v.push_back(ev);
                     *a = ev.first; *b = ev.second;
                 };
             }
-            dph_launch_coarse_filter(p->xp, nq, p->cent, p->cent_hi, p->xp_hi, p->cent_pk, p->xp_pk, p->nlist, nprobe, p->cnorm_max, p->scores, lmask,
-                                     DPH_UNIT_WORDS, by_rows ? p->probe : nullptr, nprobe, &p->coarse_cs, &p->coarse_cf, st, src, p->overflow, p->coarse_filter, p->cent_frag, p->cent_pieces, p->cnorm, p->cnorm_cap, p->coarse_teams);
+            dph_launch_coarse_filter(p->s.xp, nq, p->cent, p->cent_hi, p->s.xp_hi, p->cent_pk, p->s.xp_pk, p->nlist, nprobe, p->cnorm_max, p->s.scores, lmask,
+                                     DPH_UNIT_WORDS, by_rows ? p->s.probe : nullptr, nprobe, &p->coarse_cs, &p->coarse_cf, st, src, p->s.overflow, p->coarse_filter, p->cent_frag, p->cent_pieces, p->cnorm, p->cnorm_cap, p->coarse_teams);
         }
         else
-            dph_launch_coarse_presplit(p->xp, 0, nq, nullptr, 0, p->cent, p->nlist, nprobe, p->cnorm_max, p->scores, lmask, DPH_UNIT_WORDS,
-                                       nullptr, 0, nullptr, by_rows ? p->probe : nullptr, nprobe, p->cent_pk, p->cent_pk ? p->xp_pk : nullptr, &p->coarse_cs, st,
-                                       true, p->overflow);
+            dph_launch_coarse_presplit(p->s.xp, 0, nq, nullptr, 0, p->cent, p->nlist, nprobe, p->cnorm_max, p->s.scores, lmask, DPH_UNIT_WORDS,
+                                       nullptr, 0, nullptr, by_rows ? p->s.probe : nullptr, nprobe, p->cent_pk, p->cent_pk ? p->s.xp_pk : nullptr, &p->coarse_cs, st,
+                                       true, p->s.overflow);
         pq_scan_args a;
-        a.xp = p->xp; a.cent = p->cent; a.lut = p->lut; a.codes = p->codes; a.list_off = p->list_off;
-        a.pairs = p->pairs; a.n_pairs = p->counters + 0; a.next = p->counters + 1; a.pair_cap = p->pair_cap;
+        a.xp = p->s.xp; a.cent = p->cent; a.lut = p->s.lut; a.codes = p->codes; a.list_off = p->list_off;
+        a.pairs = p->s.pairs; a.n_pairs = p->s.counters + 0; a.next = p->s.counters + 1; a.pair_cap = p->pair_cap;
         a.M = p->M; a.seg = pq_seg(p); a.k = k; a.by_residual = p->by_residual;
-        a.bound = p->bound; a.cand_count = p->cand_count; a.cand = p->cand; a.cand_cap = p->cand_cap; a.overflow = p->overflow;
+        a.bound = p->s.bound; a.cand_count = p->s.cand_count; a.cand = p->s.cand; a.cand_cap = p->cand_cap; a.overflow = p->s.overflow;
         a.prof = p->phase_prof && p->phase_wgs >= cus ? p->phase_prof : nullptr;
         a.split_lut = p->split_lut;
-        a.units = p->units; a.n_units = p->counters + 2; a.unit_cap = p->unit_cap;
+        a.units = p->s.units; a.n_units = p->s.counters + 2; a.unit_cap = p->unit_cap;
         if (by_rows) {
             const int upr = (nprobe + PQ_GROUP - 1) / PQ_GROUP;
-            hipLaunchKernelGGL(pq_units_kernel, dim3((nq * upr + 3) / 4), dim3(256), 0, st, p->probe, nprobe, upr, nq * upr, p->list_off, a.seg, p->units,
-                               p->counters + 2, p->unit_cap, p->overflow);
-            if (p->M <= 96) hipLaunchKernelGGL(pq_adc_rows_kernel<6>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a, p->probe, nprobe, upr);
-            else hipLaunchKernelGGL(pq_adc_rows_kernel<8>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a, p->probe, nprobe, upr);
+            hipLaunchKernelGGL(pq_units_kernel, dim3((nq * upr + 3) / 4), dim3(256), 0, st, p->s.probe, nprobe, upr, nq * upr, p->list_off, a.seg, p->s.units,
+                               p->s.counters + 2, p->unit_cap, p->s.overflow);
+            if (p->M <= 96) hipLaunchKernelGGL(pq_adc_rows_kernel<6>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a, p->s.probe, nprobe, upr);
+            else hipLaunchKernelGGL(pq_adc_rows_kernel<8>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a, p->s.probe, nprobe, upr);
         } else {
-            hipLaunchKernelGGL(pq_pairs_kernel, dim3((p->nlist + 255) / 256), dim3(256), 0, st, p->listmask, DPH_UNIT_WORDS, p->nlist,
-                               p->list_off, a.seg, p->pairs, p->counters + 0, p->pair_cap, p->overflow);
+            hipLaunchKernelGGL(pq_pairs_kernel, dim3((p->nlist + 255) / 256), dim3(256), 0, st, p->s.listmask, DPH_UNIT_WORDS, p->nlist,
+                               p->list_off, a.seg, p->s.pairs, p->s.counters + 0, p->pair_cap, p->s.overflow);
             if (p->M <= 96) hipLaunchKernelGGL(pq_adc_kernel<6>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a);
             else hipLaunchKernelGGL(pq_adc_kernel<8>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a);
         }
-        hipLaunchKernelGGL(pq_final_kernel, dim3(nq), dim3(PQ_THREADS), 0, st, p->cand, p->cand_count, p->cand_cap, p->overflow, p->ids,
-                           (int)q0, k, D, I, status, (const int32_t*)p->nf);
+        hipLaunchKernelGGL(pq_final_kernel, dim3(nq), dim3(PQ_THREADS), 0, st, p->s.cand, p->s.cand_count, p->cand_cap, p->s.overflow, p->ids,
+                           (int)q0, k, D, I, status, (const int32_t*)p->s.nf);
     }
-    PQCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return DPH_OK;
 }
 
 int dph_pq_reconstruct_dev(dph_pq* p, const int64_t* ids_dev, int64_t n, float* out_dev, int32_t* found_dev, hipStream_t st) {
-    if (!p || !p->finalized) return pq_fail(DPH_E_STATE, "PQ reconstruct: index not finalized");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ reconstruct: index not finalized");
+    HIPCHK(hipSetDevice(p->device));
     if (n <= 0) return DPH_OK;
     pq_store s{p->cent, p->pqc, p->codes, p->list_off, p->dm_ids, p->dm_pos, p->ntotal, p->nlist, p->M, p->dsub, p->by_residual};
     hipLaunchKernelGGL(pq_reconstruct_kernel, dim3((unsigned)n), dim3(256), 0, st, s, ids_dev, n, out_dev, found_dev);
-    PQCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return DPH_OK;
 }
 
@@ -1336,20 +1314,20 @@ int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf,
                   const int32_t* doc, const int32_t* word, const float* first, const int32_t* row2doc, const int32_t* row2word,
                   const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off, const int32_t* f2o, int32_t* pred_word,
                   double* best, int32_t* argslot, float* vecs, hipStream_t st) {
-    if (!p || !p->finalized) return pq_fail(DPH_E_STATE, "PQ window: index not finalized");
-    PQCHK(hipSetDevice(p->device));
+    if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ window: index not finalized");
+    HIPCHK(hipSetDevice(p->device));
     if (n_q <= 0) return DPH_OK;
     if (n_q > p->qrot_rows) {
-        if (p->qrot) { (void)hipFree(p->qrot); p->qrot = nullptr; p->qrot_rows = 0; }
-        PQCHK(hipMalloc((void**)&p->qrot, (size_t)n_q * DPH_DIM * 4));
+        p->qrot_rows = 0;
+        HIPCHK(p->qrot.alloc((size_t)n_q * DPH_DIM));
         p->qrot_rows = n_q;
     }
-    if (pq_launch_transform(qhalf, p->At, n_q, nullptr, p->qrot, nullptr, nullptr, p->device, st)) return pq_fail(DPH_E_HIP, "PQ window: hipFuncSetAttribute(pq_transform_kernel)");
+    if (pq_launch_transform(qhalf, p->At, n_q, nullptr, p->qrot, nullptr, nullptr, p->device, st)) return fail(DPH_E_HIP, "PQ window: hipFuncSetAttribute(pq_transform_kernel)");
     pq_store s{p->cent, p->pqc, p->codes, p->list_off, p->dm_ids, p->dm_pos, p->ntotal, p->nlist, p->M, p->dsub, p->by_residual};
     const int64_t n_cand = n_q * k;
     hipLaunchKernelGGL(pq_window_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, s, idmap, p->qrot, n_cand, k, L,
                        ids, doc, word, first, row2doc, row2word, doc_ids, n_docs, f2o_off, f2o, pred_word, best, argslot, vecs);
     if (vecs && p->A) hipLaunchKernelGGL(pq_unrotate_kernel, dim3((unsigned)(2 * n_cand)), dim3(256), 0, st, vecs, p->A, 2 * n_cand);
-    PQCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return DPH_OK;
 }
