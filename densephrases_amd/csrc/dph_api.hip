@@ -128,7 +128,7 @@ struct dph_scratch {
         dev_buf<int> slot_q; dev_buf<int4> unit_recs, unit_list_recs; dev_buf<int8_t> unit_frags;
         int chunk_cap = 0, unit_cap = 0;
     } uq;
-    void* coarse_cs = nullptr;           // candidate scratch of the one-pass probe selection (dph_launch_coarse allocates it on first use)
+    dph_coarse_scratch coarse;           // of the coarse quantizer (dph_launch_coarse allocates what it needs on first use)
     dev_buf<long long> kmeans_sums; int kmeans_nlist = 0;        // [nlist,768] integer sums of a k-means update
     dph_search_stats stats{};
     bool stats_pending = false;          // device counters of the last device-pointer call not read back yet
@@ -140,7 +140,6 @@ struct dph_scratch {
     dph_event_pairs prof_free;
     // the two-stage form of a search (dph_search_prepare_dev / dph_search_finish_dev): what the prepare stage left behind
     struct prepared { bool valid = false; int64_t n = 0; int k = 0; const int* tau = nullptr; int fuse_stride = 0; int qb = 1; } prep;
-    ~dph_scratch() { if (coarse_cs) (void)hipFree(coarse_cs); }
 };
 
 struct dph_index {
@@ -1113,6 +1112,16 @@ static int64_t fused_scan_plan(int64_t n_tiles, int stride, unsigned* m_out) {
     return visit;
 }
 
+// what every coarse search of a shard shares: its quantizer, the query rows, the score scratch (the caller adds masks and gate)
+static dph_coarse_args coarse_args(const dph_shard& sh, const float* x, int q0, int n_q, int nprobe, float* scores) {
+    dph_coarse_args c;
+    c.x = x; c.q0 = q0; c.n_q = n_q;
+    c.centroids = sh.centroids; c.nlist = sh.nlist; c.nprobe = nprobe; c.cnorm_max = sh.cnorm_max;
+    c.scores = scores;
+    c.tile_list = sh.tile_list; c.n_tiles = sh.n_tiles;
+    return c;
+}
+
 static int run_pass(dph_index* h, dph_pass p, int k, int nprobe, const int32_t* tau_ext, int32_t* top_out,
                     const int* rowmap, float* D, int64_t* I, int32_t* status, double* bound_out, int32_t* ik_out,
                     int32_t* fail_out, hipStream_t st, int phase = 0) {
@@ -1124,17 +1133,20 @@ static int run_pass(dph_index* h, dph_pass p, int k, int nprobe, const int32_t* 
         int rc = ensure_units(h, nprobe);
         if (rc) return rc;
         const dph_scratch::unit_queue& uq = h->sc.uq;
-        dph_launch_coarse(p.x, p.q0, p.n_q, nullptr, 0, sh.centroids, sh.nlist, nprobe, sh.cnorm_max, ivf.coarse_scores,
-                          ivf.listmask_u, DPH_UNIT_WORDS, sh.tile_list, sh.n_tiles, nullptr, &h->sc.coarse_cs, st);
+        dph_coarse_args c = coarse_args(sh, p.x, p.q0, p.n_q, nprobe, ivf.coarse_scores);
+        c.listmask = ivf.listmask_u; c.mask_words = DPH_UNIT_WORDS;
+        dph_launch_coarse(c, h->sc.coarse, st);
         dph_launch_units_build(ivf.listmask_u, sh.nlist, sh.list_tile0, p.q1, p.q0, uq.chunk_cap, uq.unit_cap, ivf.unit_counts,
-                               ivf.unit_counts + 4, uq.slot_q, uq.unit_recs, uq.unit_list_recs, uq.unit_frags, ivf.unit_offsets, h->tune.ivf_spread, st, dph_frag_x16(sh.aux_lay.stride));
+                               uq.slot_q, uq.unit_recs, uq.unit_list_recs, uq.unit_frags, ivf.unit_offsets, h->tune.ivf_spread, st, dph_frag_x16(sh.aux_lay.stride));
         p.unit_recs = uq.unit_recs; p.unit_list_recs = uq.unit_list_recs; p.unit_counts = ivf.unit_counts; p.unit_next = ivf.unit_counts + 4; p.unit_launch = 0;
         p.slot_q = uq.slot_q; p.unit_frags = uq.unit_frags; p.listmask = ivf.listmask_u; p.tile_list = sh.tile_list;
         p.mask_words = DPH_UNIT_WORDS;
     } else if (sh.row_ids) {
         if (nprobe > 0) {
-            dph_launch_coarse(p.x, p.q0, p.n_q, p.gate, p.gate_base, sh.centroids, sh.nlist, nprobe, sh.cnorm_max, ivf.coarse_scores, ivf.listmask, 8,
-                              sh.tile_list, sh.n_tiles, ivf.tilemask, &h->sc.coarse_cs, st);
+            dph_coarse_args c = coarse_args(sh, p.x, p.q0, p.n_q, nprobe, ivf.coarse_scores);
+            c.gate = p.gate; c.gate_base = p.gate_base;
+            c.listmask = ivf.listmask; c.mask_words = 8; c.tilemask = ivf.tilemask;
+            dph_launch_coarse(c, h->sc.coarse, st);
             p.tilemask = ivf.tilemask;
         } else {
             p.tilemask = sh.onesmask;
@@ -1261,8 +1273,10 @@ static int check_search_args(dph_index* h, const void* x, int64_t n, int k, int 
 static void launch_exact_fallback(dph_index* h, int k, int nprobe, float* D, int64_t* I, int32_t* status, int rounds, hipStream_t st) {
     const unsigned* mask = nullptr;
     if (h->sh->row_ids && nprobe > 0) {
-        dph_launch_coarse(h->sc.exact_x, 0, DPH_EXACT_ROWS_DEV, h->sc.counters + 1, 0, h->sh->centroids, h->sh->nlist, nprobe, h->sh->cnorm_max,
-                          h->sc.ivf.coarse_scores, h->sc.ivf.listmask, 8, h->sh->tile_list, h->sh->n_tiles, h->sc.ivf.tilemask, &h->sc.coarse_cs, st);
+        dph_coarse_args c = coarse_args(*h->sh, h->sc.exact_x, 0, DPH_EXACT_ROWS_DEV, nprobe, h->sc.ivf.coarse_scores);
+        c.gate = h->sc.counters + 1;
+        c.listmask = h->sc.ivf.listmask; c.mask_words = 8; c.tilemask = h->sc.ivf.tilemask;
+        dph_launch_coarse(c, h->sc.coarse, st);
         mask = h->sc.ivf.tilemask;
     }
     dph_launch_exact(h->sh->db, h->sh->n_rows, make_idmap(h->sh), h->sc.exact_x, h->sh->lut_dev, h->sc.exact_rows, h->sc.counters + 1, DPH_EXACT_ROWS_DEV,

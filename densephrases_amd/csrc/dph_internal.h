@@ -266,21 +266,49 @@ struct dph_select_args {
     int* reselect_count;                // ... counting the rows it certifies
 };
 void dph_launch_select(const dph_pass& p, const dph_select_args& a, hipStream_t st);
-// listmask[nlist][mask_words]; tilemask (8 words per tile, mask_words == 8 only) may be NULL.  cs_slot: the caller's (one per index
-// handle) slot for the candidate scratch of the one-pass probe selection -- allocated here on first use, hipFree'd by the owner;
-// NULL = no scratch, long score rows take the full three-pass selection
-void dph_launch_coarse(const float* x_dev, int q0, int n_q, const int* gate, int gate_base, const float* centroids, int nlist,
-                       int nprobe, double cnorm_max, float* scores, unsigned* listmask, int mask_words, const int32_t* tile_list,
-                       int64_t n_tiles, unsigned* tilemask, void** cs_slot, hipStream_t st);
-void dph_launch_coarse_lists(const float* x_dev, int q0, int n_q, const int* gate, int gate_base, const float* centroids, int nlist,
-                             int nprobe, double cnorm_max, float* scores, unsigned* listmask, int mask_words,
-                             const int32_t* tile_list, int64_t n_tiles, unsigned* tilemask, int* probe_out, int probe_stride,
-                             void** cs_slot, hipStream_t st);
-void dph_launch_coarse_presplit(const float* x_dev, int q0, int n_q, const int* gate, int gate_base, const float* centroids, int nlist,
-                                int nprobe, double cnorm_max, float* scores, unsigned* listmask, int mask_words,
-                                const int32_t* tile_list, int64_t n_tiles, unsigned* tilemask, int* probe_out, int probe_stride,
-                                const unsigned* c_pk, const unsigned* x_pk, void** cs_slot, hipStream_t st, bool clear_mask = true,
-                                unsigned* row_fail = nullptr);
+// ---- the coarse quantizer (dph_ivf.hip)
+// Its scratch, one per index handle (two handles searched from two threads never share it): allocated by the launchers on first use (they
+// know the sizes), never shrunk, freed with the handle.  Each part is held whole or not at all -- a part that cannot be allocated is
+// tried again by the next call, which meanwhile takes the path that does without it.
+struct dph_coarse_counters {            // cleared by one memset per filter pass
+    unsigned cand_cnt[DPH_PASS_MAX];    // candidates of every row
+    unsigned est[DPH_PASS_MAX];         // threshold estimate (score key) of every row
+    unsigned pool_count, fail;          // triples in the linear pool; 1 = the pass fails over to the chain
+    int gate;                           // rows the fail-over chain serves: all of the pass or none
+    unsigned sink;                      // takes the pool statistic when DPH_CF_KEEP_POOL fills pool_count itself
+    unsigned spare[12];
+};
+struct dph_coarse_scratch {
+    struct chain_part {                 // one-pass probe selection over long score rows
+        dev_buf<uint2> cand; dev_buf<unsigned> cand_cnt, est;      // [DPH_PASS_MAX][CS_CAND] (list, key), [DPH_PASS_MAX], [DPH_PASS_MAX]
+    } chain;
+    struct filter_part {                // the filter form; its candidate lists are its own (the fail-over chain runs behind it)
+        dev_buf<float> sample;                                      // [DPH_PASS_MAX][CF_SAMPLE] scores of the sampled lists
+        dev_buf<uint2> pool_lk; dev_buf<unsigned short> pool_q;     // linear pool: (list, key) and query row of up to CS_CAND triples per row
+        dev_buf<uint2> cand;                                        // [DPH_PASS_MAX][CS_CAND]
+        dev_buf<dph_coarse_counters> cnt;                           // [1]
+        // the scan form (variant 5): pair pool and its chunk fills, per-wave statistics, queue counters, query fragments of a whole pass
+        dev_buf<uint2> pairs; dev_buf<unsigned> chunk_fill, wave_counts; dev_buf<int> counters; dev_buf<uint4> qfrag;
+    } filter;
+};
+// One coarse search: the nprobe best lists of query rows [q0, q0 + n_q) of x [.., 768], as bits of listmask [nlist][mask_words] (bit = row
+// of the pass; NULL: none), per tile in tilemask (8 words per tile, mask_words == 8 only; NULL: none) and / or as a list per row in
+// probe_out [n_q][probe_stride] (-1 padded, order unspecified: what a scan that groups its work by query row walks; NULL: none).
+struct dph_coarse_args {
+    const float* x = nullptr; int q0 = 0; int n_q = 0;
+    const int* gate = nullptr; int gate_base = 0;
+    const float* centroids = nullptr; int nlist = 0; int nprobe = 0; double cnorm_max = 0.0;
+    float* scores = nullptr;                                    // [n_q][nlist] scratch
+    unsigned* listmask = nullptr; int mask_words = 0;
+    const int32_t* tile_list = nullptr; int64_t n_tiles = 0; unsigned* tilemask = nullptr;
+    int* probe_out = nullptr; int probe_stride = 0;
+    // packed bf16 hi / lo images (dph_launch_bf16_split) of the centroids [nlist,768] and of the query rows [>= q0 + n_q, 768] when the
+    // caller keeps them (dph_pq.hip): the long-quantizer GEMM then unpacks instead of splitting
+    const unsigned* c_pk = nullptr; const unsigned* x_pk = nullptr;
+    unsigned* row_fail = nullptr;                               // [n_q] set for a row whose error band overflows the re-rank (NULL: the band is cut)
+    bool clear_mask = true;                                     // false: OR into the listmask as it is
+};
+void dph_launch_coarse(const dph_coarse_args& a, dph_coarse_scratch& s, hipStream_t st);
 // The int8 scans multiply with v_mfma_i32_16x16x64_i8 (dph_scan.hip, round 6), and the high-digit query fragments are written in
 // that instruction's operand order: entry [2 s + h][lane] (16 bytes) of a group of 32 query rows = bytes 64 s + 16 (lane >> 4) .. + 15
 // of query row 16 h + (lane & 15).  (DPH_SCAN_X16 = 0 builds the 32 x 32 x 32 kernels of rounds 1-5 for A/B timing: entry [ks][lane] =
@@ -291,16 +319,19 @@ void dph_launch_coarse_presplit(const float* x_dev, int q0, int n_q, const int* 
 __host__ __device__ static inline bool dph_frag_x16(int aux_stride) { (void)aux_stride; return DPH_SCAN_X16 != 0; }
 // hands out a fresh (start, stop) event pair per bracketed launch (profiling; next == NULL: none)
 struct dph_event_source { void* ctx; void (*next)(void* ctx, hipEvent_t* a, hipEvent_t* b); };
-// long quantizers, the filter form: one-product bf16 GEMM with the threshold test in its epilogue (dph_ivf.hip)
-void dph_launch_coarse_filter(const float* x_dev, int n_q, const float* centroids, const unsigned short* c_hi, const unsigned short* x_hi,
-                              const unsigned* c_pk, const unsigned* x_pk, int nlist, int nprobe, double cnorm_max, float* scores,
-                              unsigned* listmask, int mask_words, int* probe_out, int probe_stride, void** cs_slot, void** cf_slot,
-                              hipStream_t st, dph_event_source prof = dph_event_source{nullptr, nullptr}, unsigned* row_fail = nullptr,
-                              int variant = 1 /* 2: the centroid stream loaded non-temporal, 3: centroids straight into registers from c_frag,
-                                                 5: the filter scan over c_pieces (<= 128 query rows; more: variant 3) */,
-                              const unsigned short* c_frag = nullptr, const unsigned short* c_pieces = nullptr,
-                              const float* cnorm = nullptr /* [nlist] ||c_l||_2 (device) */, double cnorm_cap = 0.0 /* lists longer than this get exact scores */,
-                              int coarse_teams = 1 /* variant 5, more than 128 rows: one launch of workgroup teams sharing tiles through L2 (dph_scan.hip MODE 4) */);
+// long quantizers, the filter form: one-product bf16 GEMM with the threshold test in its epilogue (dph_ivf.hip).  A whole pass from row 0
+// (q0 = 0, no gate, no tiles); c_pk / x_pk feed its fail-over chain.
+struct dph_coarse_filter_args : dph_coarse_args {
+    const unsigned short* c_hi = nullptr; const unsigned short* x_hi = nullptr;       // bf16 images of the centroids (tiled) and of the query rows
+    int variant = 1;                    // 2: the centroid stream loaded non-temporal, 3: centroids straight into registers from c_frag,
+                                        // 5: the filter scan over c_pieces
+    const unsigned short* c_frag = nullptr; const unsigned short* c_pieces = nullptr;
+    const float* cnorm = nullptr;       // [nlist] ||c_l||_2 (device)
+    double cnorm_cap = 0.0;             // lists longer than this get exact scores
+    int teams = 1;                      // variant 5, more than 128 rows: one launch of workgroup teams sharing tiles through L2 (dph_scan.hip MODE 4)
+    dph_event_source prof{nullptr, nullptr};
+};
+void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratch& s, hipStream_t st);
 void dph_launch_coarse_scan_teams(const void* img, int64_t n_lists, const void* qfrag, int n_q, int n_groups, const unsigned* est_keys, uint2* pairs,
                                   unsigned* chunk_fill, unsigned* wave_counts, int* counters, int grid, hipStream_t st);
 // variant 5: the coarse quantizer as a filter SCAN (dph_scan.hip MODE 3) over the piece-major bf16 image
@@ -313,16 +344,16 @@ void dph_launch_coarse_scan(const void* img, int64_t n_lists, const void* qfrag,
 // the fragment-major bf16 image variant 3 streams (dph_bf16_frag_rows(n) rows allocated)
 void dph_launch_bf16_frag(const float* v, int64_t n_rows, unsigned short* out, hipStream_t st);
 int64_t dph_bf16_frag_rows(int64_t n_rows);
-int dph_coarse_filter_debug(void* cf_slot, unsigned out[2]);
-long long dph_coarse_filter_debug_pool(void* cf_slot, unsigned* lk_host, unsigned short* q_host, long long cap);
+int dph_coarse_filter_debug(const dph_coarse_scratch& s, unsigned out[2]);
+long long dph_coarse_filter_debug_pool(const dph_coarse_scratch& s, unsigned* lk_host, unsigned short* q_host, long long cap);
 // bf16 image of a [n_rows, 768] fp32 matrix; tiled = 1: the tile-major layout the filter GEMM streams (dph_bf16_hi_rows(n, 1) rows allocated)
 void dph_launch_bf16_hi(const float* v, int64_t n_rows, int tiled, unsigned short* hi, hipStream_t st);
 int64_t dph_bf16_hi_rows(int64_t n_rows, int tiled);
 void dph_launch_bf16_split(const float* v, int64_t n_elems, unsigned* packed, hipStream_t st);
 // work queue of a unit-scan pass from the probe masks: chunks, slot tables, unit records, gathered fragments
 void dph_launch_units_build(const unsigned* listmask, int nlist, const int* list_tile0, const int8_t* q1, int q0,
-                            int chunk_cap, int unit_cap, int* unit_counts, int* unit_next, int* slot_q, int4* unit_recs,
-                            int4* unit_list_recs, int8_t* unit_frags, int2* unit_offsets, int spread, hipStream_t st, bool x16);
+                            int chunk_cap, int unit_cap, int* unit_counts, int* slot_q, int4* unit_recs, int4* unit_list_recs,
+                            int8_t* unit_frags, int2* unit_offsets, int spread, hipStream_t st, bool x16);
 // list assignment (arg-max over the centroids, fused: no score matrix); rows = fp32 [n,768] or int8 rows + the shard's LUT
 void dph_launch_assign(const void* rows, bool rows_int8, const float* lut, int64_t n, const float* centroids, int nlist,
                        const float* bias, int32_t* best, float* gap, hipStream_t st);

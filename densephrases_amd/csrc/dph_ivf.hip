@@ -121,12 +121,10 @@ void dph_launch_bf16_split(const float* v, int64_t n_elems, unsigned* packed, hi
         hipLaunchKernelGGL(dph_bf16_split_kernel, dim3((unsigned)std::min<int64_t>((n_elems + 255) / 256, 1 << 16)), dim3(256), 0, st, v, n_elems, packed);
 }
 
-template <bool PRE>
 __global__ __launch_bounds__(256) void dph_coarse_gemm_bf16x3_kernel(const float* __restrict__ x, int q0, int n_q_host,
                                                                      const int* __restrict__ gate, int gate_base,
                                                                      const float* __restrict__ centroids, int nlist,
-                                                                     float* __restrict__ scores, const unsigned* __restrict__ c_pk,
-                                                                     const unsigned* __restrict__ x_pk) {
+                                                                     float* __restrict__ scores) {
     __shared__ __attribute__((aligned(16))) unsigned short a_hi[CG_LISTS * CG3_LD], a_lo[CG_LISTS * CG3_LD];
     __shared__ __attribute__((aligned(16))) unsigned short b_hi[CG_QROWS * CG3_LD], b_lo[CG_QROWS * CG3_LD];
     const int n_q = dph_gated_rows(gate, gate_base, n_q_host);
@@ -144,17 +142,6 @@ __global__ __launch_bounds__(256) void dph_coarse_gemm_bf16x3_kernel(const float
         for (int i = 0; i < 4; ++i) {
             const int row = (tid >> 3) + 32 * i, c4 = (tid & 7) * 4;
             const int l = l0 + row, q = qb0 + row;
-            if constexpr (PRE) {
-                const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-                const uint4 av = l < nlist ? *(const uint4*)(c_pk + (int64_t)l * DPH_DIM + k0 + c4) : z;
-                const uint4 bv = q < n_q ? *(const uint4*)(x_pk + (int64_t)(q0 + q) * DPH_DIM + k0 + c4) : z;
-                // word = hi << 16 | lo: the hi halves of two elements / their lo halves into one register each
-                *(uint2*)(a_hi + row * CG3_LD + c4) = make_uint2(__builtin_amdgcn_perm(av.y, av.x, 0x07060302u), __builtin_amdgcn_perm(av.w, av.z, 0x07060302u));
-                *(uint2*)(a_lo + row * CG3_LD + c4) = make_uint2(__builtin_amdgcn_perm(av.y, av.x, 0x05040100u), __builtin_amdgcn_perm(av.w, av.z, 0x05040100u));
-                *(uint2*)(b_hi + row * CG3_LD + c4) = make_uint2(__builtin_amdgcn_perm(bv.y, bv.x, 0x07060302u), __builtin_amdgcn_perm(bv.w, bv.z, 0x07060302u));
-                *(uint2*)(b_lo + row * CG3_LD + c4) = make_uint2(__builtin_amdgcn_perm(bv.y, bv.x, 0x05040100u), __builtin_amdgcn_perm(bv.w, bv.z, 0x05040100u));
-                continue;
-            }
             const float4 av = l < nlist ? *(const float4*)(centroids + (int64_t)l * DPH_DIM + k0 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
             const float4 bv = q < n_q ? *(const float4*)(x + (int64_t)(q0 + q) * DPH_DIM + k0 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
             unsigned short h[4], lw[4];
@@ -1190,244 +1177,200 @@ __global__ __launch_bounds__(256) void dph_tilemask_kernel(const int32_t* __rest
     }
 }
 
-void dph_launch_coarse(const float* x_dev, int q0, int n_q, const int* gate, int gate_base, const float* centroids, int nlist,
-                       int nprobe, double cnorm_max, float* scores, unsigned* listmask, int mask_words, const int32_t* tile_list,
-                       int64_t n_tiles, unsigned* tilemask, void** cs_slot, hipStream_t st) {
-    dph_launch_coarse_lists(x_dev, q0, n_q, gate, gate_base, centroids, nlist, nprobe, cnorm_max, scores, listmask, mask_words,
-                            tile_list, n_tiles, tilemask, nullptr, 0, cs_slot, st);
+// Dynamic LDS beyond the default limit is granted per kernel and device: asked for once (`done`: a static of the call site -- zero-
+// initialised; handles are searched from several threads), asked again by the next call when it was refused.
+static void cg_allow_lds(const void* kernel, const char* name, size_t bytes, int dev, std::atomic<bool> (&done)[64]) {
+    if (dev >= 0 && dev < 64 && done[dev]) return;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(%s, %zu B of LDS): %s\n", name, bytes, hipGetErrorString(e));
+    if (dev >= 0 && dev < 64) done[dev] = e == hipSuccess;
+}
+#define CG_ALLOW_LDS(KERNEL, BYTES, DEV)                                            \
+    do {                                                                            \
+        static std::atomic<bool> done_[64];                                         \
+        cg_allow_lds((const void*)KERNEL, #KERNEL, (BYTES), (DEV), done_);          \
+    } while (0)
+#define CS_LDS ((size_t)2 * CS_CAND * 4)        // dynamic LDS of the select kernel (static + dynamic exceed 64 KiB)
+
+static void cs_select_allow_lds(int dev) { CG_ALLOW_LDS(dph_coarse_select_kernel, CS_LDS, dev); }
+
+// the parts of the scratch (dph_internal.h): all of a part or nothing; a failed hipMalloc is not the caller's error
+static bool ensure_chain(dph_coarse_scratch::chain_part& c) {
+    if (c.est) return true;                         // (allocated last)
+    const size_t rows = DPH_PASS_MAX;
+    const bool ok = c.cand.alloc(rows * CS_CAND) == hipSuccess && c.cand_cnt.alloc(rows) == hipSuccess && c.est.alloc(rows) == hipSuccess;
+    if (!ok) { c = dph_coarse_scratch::chain_part{}; (void)hipGetLastError(); }
+    return ok;
+}
+static bool ensure_filter(dph_coarse_scratch::filter_part& f) {
+    if (f.qfrag) return true;                       // (allocated last)
+    const size_t rows = DPH_PASS_MAX;
+    // (the scan form's buffers always, whether or not the first call brings the piece image: a later call that does must find them.
+    // Wave statistics for 256 CUs; the fragments of a whole pass: the teams form)
+    const bool ok = f.sample.alloc(rows * CF_SAMPLE) == hipSuccess && f.pool_lk.alloc(rows * CS_CAND) == hipSuccess &&
+                    f.pool_q.alloc(rows * CS_CAND) == hipSuccess && f.cand.alloc(rows * CS_CAND) == hipSuccess && f.cnt.alloc(1) == hipSuccess &&
+                    f.pairs.alloc((size_t)DPH_POOL_CHUNKS * DPH_CHUNK_PAIRS) == hipSuccess && f.chunk_fill.alloc(DPH_POOL_CHUNKS) == hipSuccess &&
+                    f.wave_counts.alloc(256 * 4 * 2) == hipSuccess && f.counters.alloc(64) == hipSuccess &&
+                    f.qfrag.alloc((size_t)(DPH_PASS_MAX / DPH_QROWS) * 4 * 2 * DPH_QGROUP_FRAG_BYTES / sizeof(uint4)) == hipSuccess;
+    if (!ok) { f = dph_coarse_scratch::filter_part{}; (void)hipGetLastError(); }
+    return ok;
 }
 
-// the same, and additionally the probed lists of every query row as a list: probe_out [n_q][probe_stride] (-1 padded, order
-// unspecified) -- what a scan that groups its work by query row walks (dph_pq.hip, many short lists)
-void dph_launch_coarse_lists(const float* x_dev, int q0, int n_q, const int* gate, int gate_base, const float* centroids, int nlist,
-                             int nprobe, double cnorm_max, float* scores, unsigned* listmask, int mask_words,
-                             const int32_t* tile_list, int64_t n_tiles, unsigned* tilemask, int* probe_out, int probe_stride,
-                             void** cs_slot, hipStream_t st) {
-    dph_launch_coarse_presplit(x_dev, q0, n_q, gate, gate_base, centroids, nlist, nprobe, cnorm_max, scores, listmask, mask_words,
-                               tile_list, n_tiles, tilemask, probe_out, probe_stride, nullptr, nullptr, cs_slot, st, true, nullptr);
-}
-
-// ... and with the packed bf16 hi / lo images (dph_launch_bf16_split) of the centroids [nlist,768] and of the query rows
-// [>= q0 + n_q, 768] when the caller keeps them (dph_pq.hip): the long-quantizer GEMM then unpacks instead of splitting
-void dph_launch_coarse_presplit(const float* x_dev, int q0, int n_q, const int* gate, int gate_base, const float* centroids, int nlist,
-                                int nprobe, double cnorm_max, float* scores, unsigned* listmask, int mask_words,
-                                const int32_t* tile_list, int64_t n_tiles, unsigned* tilemask, int* probe_out, int probe_stride,
-                                const unsigned* c_pk, const unsigned* x_pk, void** cs_slot, hipStream_t st, bool clear_mask,
-                                unsigned* row_fail) {
-    if (clear_mask && listmask) (void)hipMemsetAsync(listmask, 0, (size_t)nlist * mask_words * 4, st);
-    const bool bf16x3 = nlist >= CG_BF16X3_MIN;
-    const dim3 gg((nlist + CG_LISTS - 1) / CG_LISTS, (n_q + CG_QROWS - 1) / CG_QROWS);
-    if (bf16x3 && c_pk && x_pk) {
+// the chain: score GEMM (f32, or bf16x3 from CG_BF16X3_MIN lists on), probe selection, tile masks
+void dph_launch_coarse(const dph_coarse_args& a, dph_coarse_scratch& s, hipStream_t st) {
+    if (a.clear_mask && a.listmask) (void)hipMemsetAsync(a.listmask, 0, (size_t)a.nlist * a.mask_words * 4, st);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const bool bf16x3 = a.nlist >= CG_BF16X3_MIN;
+    const dim3 gg((a.nlist + CG_LISTS - 1) / CG_LISTS, (a.n_q + CG_QROWS - 1) / CG_QROWS);
+    if (bf16x3 && a.c_pk && a.x_pk) {
         const size_t lds3 = (size_t)4 * CG_LISTS * CG3P_LD * 2;
-        static std::atomic<bool> attr3[64];      // (statics: zero-initialised; handles are searched from several threads)
-        int dev3 = 0;
-        (void)hipGetDevice(&dev3);
-        if (dev3 < 0 || dev3 >= 64 || !attr3[dev3]) {
-            const hipError_t e = hipFuncSetAttribute((const void*)dph_coarse_gemm_bf16x3_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(dph_coarse_gemm_bf16x3_pipe_kernel, %zu B of LDS): %s\n", lds3, hipGetErrorString(e));
-            if (dev3 >= 0 && dev3 < 64) attr3[dev3] = e == hipSuccess;
-        }
-        hipLaunchKernelGGL(dph_coarse_gemm_bf16x3_pipe_kernel, gg, dim3(256), lds3, st, q0, n_q, gate, gate_base, nlist, scores, c_pk, x_pk);
+        CG_ALLOW_LDS(dph_coarse_gemm_bf16x3_pipe_kernel, lds3, dev);
+        hipLaunchKernelGGL(dph_coarse_gemm_bf16x3_pipe_kernel, gg, dim3(256), lds3, st, a.q0, a.n_q, a.gate, a.gate_base, a.nlist, a.scores, a.c_pk, a.x_pk);
     }
     else if (bf16x3)
-        hipLaunchKernelGGL(dph_coarse_gemm_bf16x3_kernel<false>, gg, dim3(256), 0, st, x_dev, q0, n_q, gate, gate_base, centroids, nlist, scores,
-                           (const unsigned*)nullptr, (const unsigned*)nullptr);
+        hipLaunchKernelGGL(dph_coarse_gemm_bf16x3_kernel, gg, dim3(256), 0, st, a.x, a.q0, a.n_q, a.gate, a.gate_base, a.centroids, a.nlist, a.scores);
     else
-        hipLaunchKernelGGL(dph_coarse_gemm_kernel, dim3((nlist + CG_LISTS - 1) / CG_LISTS, (n_q + CG_QROWS - 1) / CG_QROWS), dim3(256), 0,
-                           st, x_dev, q0, n_q, gate, gate_base, centroids, nlist, scores);
-    // long score rows: candidates collected by several workgroups per row first (scratch: one allocation per index handle, sized
-    // for DPH_PASS_MAX rows, in the caller's slot -- two handles searched from two threads never share it)
-    uint2* cand_glob = nullptr; unsigned* cand_cnt = nullptr; unsigned* est = nullptr;
-    if (nlist >= CS_FAST_MIN && n_q <= DPH_PASS_MAX && cs_slot) {
-        const size_t cand_bytes = (size_t)DPH_PASS_MAX * CS_CAND * sizeof(uint2);
-        if (!*cs_slot && hipMalloc(cs_slot, cand_bytes + 2 * DPH_PASS_MAX * 4) != hipSuccess) { *cs_slot = nullptr; (void)hipGetLastError(); }
-        if (*cs_slot) {
-            cand_glob = (uint2*)*cs_slot;
-            cand_cnt = (unsigned*)((char*)*cs_slot + cand_bytes);
-            est = cand_cnt + DPH_PASS_MAX;
-            (void)hipMemsetAsync(cand_cnt, 0, (size_t)n_q * 4, st);
-            int slices = 2048 / (n_q > 0 ? n_q : 1);
-            slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
-            hipLaunchKernelGGL(dph_coarse_estimate_kernel, dim3(n_q), dim3(CS_THREADS), 0, st, scores, n_q, gate, gate_base, nlist, nprobe, est);
-            hipLaunchKernelGGL(dph_coarse_collect_kernel, dim3(n_q, slices), dim3(CS_THREADS), 0, st, scores, n_q, gate, gate_base, nlist,
-                               cand_glob, cand_cnt, est);
-        }
+        hipLaunchKernelGGL(dph_coarse_gemm_kernel, gg, dim3(256), 0, st, a.x, a.q0, a.n_q, a.gate, a.gate_base, a.centroids, a.nlist, a.scores);
+    // long score rows: candidates collected by several workgroups per row first; without the scratch they take the full three-pass selection
+    uint2* cand = nullptr; unsigned* cand_cnt = nullptr; unsigned* est = nullptr;
+    if (a.nlist >= CS_FAST_MIN && a.n_q <= DPH_PASS_MAX && ensure_chain(s.chain)) {
+        cand = s.chain.cand; cand_cnt = s.chain.cand_cnt; est = s.chain.est;
+        (void)hipMemsetAsync(cand_cnt, 0, (size_t)a.n_q * 4, st);
+        int slices = 2048 / (a.n_q > 0 ? a.n_q : 1);
+        slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
+        hipLaunchKernelGGL(dph_coarse_estimate_kernel, dim3(a.n_q), dim3(CS_THREADS), 0, st, a.scores, a.n_q, a.gate, a.gate_base, a.nlist, a.nprobe, est);
+        hipLaunchKernelGGL(dph_coarse_collect_kernel, dim3(a.n_q, slices), dim3(CS_THREADS), 0, st, a.scores, a.n_q, a.gate, a.gate_base, a.nlist,
+                           cand, cand_cnt, est);
     }
-    const size_t cs_lds = (size_t)2 * CS_CAND * 4;
-    static std::atomic<bool> cs_attr[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !cs_attr[dev]) {      // static + dynamic LDS of the select kernel exceed 64 KiB
-        const hipError_t e = hipFuncSetAttribute((const void*)dph_coarse_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_lds);
-        if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(dph_coarse_select_kernel, %zu B of LDS): %s\n", cs_lds, hipGetErrorString(e));
-        if (dev >= 0 && dev < 64) cs_attr[dev] = e == hipSuccess;
-    }
-    hipLaunchKernelGGL(dph_coarse_select_kernel, dim3(n_q), dim3(CS_THREADS), cs_lds, st, x_dev, q0, n_q, gate, gate_base, centroids,
-                       scores, nlist, nprobe, cnorm_max, listmask, mask_words, probe_out, probe_stride,
-                       1.5 * (bf16x3 ? CG_BF16X3_ERR : CG_F32_ERR), cand_glob, cand_cnt, est, (unsigned*)nullptr, row_fail);
-    if (tilemask && mask_words == 8)
-    hipLaunchKernelGGL(dph_tilemask_kernel, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, st, tile_list, n_tiles,
-                       (const uint4*)listmask, (uint4*)tilemask, gate, gate_base);
+    cs_select_allow_lds(dev);
+    hipLaunchKernelGGL(dph_coarse_select_kernel, dim3(a.n_q), dim3(CS_THREADS), CS_LDS, st, a.x, a.q0, a.n_q, a.gate, a.gate_base, a.centroids,
+                       a.scores, a.nlist, a.nprobe, a.cnorm_max, a.listmask, a.mask_words, a.probe_out, a.probe_stride,
+                       1.5 * (bf16x3 ? CG_BF16X3_ERR : CG_F32_ERR), cand, cand_cnt, est, (unsigned*)nullptr, a.row_fail);
+    if (a.tilemask && a.mask_words == 8)
+        hipLaunchKernelGGL(dph_tilemask_kernel, dim3((unsigned)((a.n_tiles + 255) / 256)), dim3(256), 0, st, a.tile_list, a.n_tiles,
+                           (const uint4*)a.listmask, (uint4*)a.tilemask, a.gate, a.gate_base);
 }
 
-// The filter form for long quantizers (comment above dph_coarse_filter_gemm_kernel).  x_dev: the (rotated) query rows of the pass
+// The filter form for long quantizers (comment above dph_coarse_filter_gemm_kernel).  a.x: the (rotated) query rows of the pass
 // [n_q][768] fp32, x_hi / c_hi their and the centroids' bf16 images, x_pk / c_pk the packed hi|lo images the fail-over chain multiplies.
-// Scratch in *cf_slot (one allocation per index handle).
-void dph_launch_coarse_filter(const float* x_dev, int n_q, const float* centroids, const unsigned short* c_hi, const unsigned short* x_hi,
-                              const unsigned* c_pk, const unsigned* x_pk, int nlist, int nprobe, double cnorm_max, float* scores,
-                              unsigned* listmask, int mask_words, int* probe_out, int probe_stride, void** cs_slot, void** cf_slot,
-                              hipStream_t st, dph_event_source prof, unsigned* row_fail, int variant,
-                              const unsigned short* c_frag, const unsigned short* c_pieces, const float* cnorm, double cnorm_cap, int coarse_teams) {
-    const int m = nlist < CF_SAMPLE ? nlist : CF_SAMPLE;
-    const int stride = nlist / m;
-    const size_t b_sample = (size_t)DPH_PASS_MAX * CF_SAMPLE * 4, b_pool_lk = (size_t)DPH_PASS_MAX * CS_CAND * 8,
-                 b_pool_q = (size_t)DPH_PASS_MAX * CS_CAND * 2, b_cand = (size_t)DPH_PASS_MAX * CS_CAND * 8, b_small = (size_t)(2 * DPH_PASS_MAX + 16) * 4;
-    // the scan form's own scratch behind the rest: pair pool, chunk fill counts, per-wave statistics, queue counters, query fragments
-    int cus_scan = 256;
-    {
-        int d = 0;
-        (void)hipGetDevice(&d);
-        (void)hipDeviceGetAttribute(&cus_scan, hipDeviceAttributeMultiprocessorCount, d);
-        if (cus_scan <= 0 || cus_scan > 256) cus_scan = 256;
-    }
-    const size_t b_pairs = (size_t)DPH_POOL_CHUNKS * DPH_CHUNK_PAIRS * 8, b_fill = (size_t)DPH_POOL_CHUNKS * 4, b_wc = (size_t)256 * 4 * 2 * 4,
-                 b_cnt = 256, b_qfrag = (size_t)(DPH_PASS_MAX / DPH_QROWS) * 4 * 2 * DPH_QGROUP_FRAG_BYTES;      // (the fragments of a whole pass: the teams form)
-    // (always reserved, whether or not the first call brings the piece image: a later call that does must find it -- ADVICE r5)
-    const size_t b_scan = b_pairs + b_fill + b_wc + b_cnt + b_qfrag;
-    if (!*cf_slot && hipMalloc(cf_slot, b_sample + b_pool_lk + b_pool_q + b_cand + b_small + 256 + b_scan) != hipSuccess) { *cf_slot = nullptr; (void)hipGetLastError(); }
-    if (!*cf_slot || n_q > DPH_PASS_MAX) {          // no scratch: the bf16x3 chain alone
-        dph_launch_coarse_presplit(x_dev, 0, n_q, nullptr, 0, centroids, nlist, nprobe, cnorm_max, scores, listmask, mask_words, nullptr, 0, nullptr,
-                                   probe_out, probe_stride, c_pk, x_pk, cs_slot, st, true, row_fail);
+void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratch& s, hipStream_t st) {
+    dph_coarse_args chain = a;                      // what the bf16x3 chain serves: the pass as it stands, or its fail-over
+    const int n_q = a.n_q, nlist = a.nlist;
+    if (!ensure_filter(s.filter) || n_q > DPH_PASS_MAX) {          // no scratch: the bf16x3 chain alone
+        dph_launch_coarse(chain, s, st);
         return;
     }
-    char* base = (char*)*cf_slot;
-    float* sample = (float*)base;
-    uint2* pool_lk = (uint2*)(base + b_sample);
-    unsigned short* pool_q = (unsigned short*)(base + b_sample + b_pool_lk);
-    uint2* cand = (uint2*)(base + b_sample + b_pool_lk + b_pool_q);
-    unsigned* small = (unsigned*)(base + b_sample + b_pool_lk + b_pool_q + b_cand);
-    unsigned* cand_cnt = small;                          // [DPH_PASS_MAX]
-    unsigned* est = small + DPH_PASS_MAX;                // [DPH_PASS_MAX]
-    unsigned* pool_count = small + 2 * DPH_PASS_MAX;     // [1]
-    unsigned* fail = pool_count + 1;                     // [1]
-    int* gate = (int*)(pool_count + 2);                  // [1]
+    const dph_coarse_scratch::filter_part& f = s.filter;
+    dph_coarse_counters* const cnt = f.cnt;
+    unsigned* const cand_cnt = cnt->cand_cnt;       // (addresses of device memory: nothing is read here)
+    unsigned* const est = cnt->est;
+    unsigned* const pool_count = &cnt->pool_count;
+    unsigned* const fail = &cnt->fail;
+    const int m = nlist < CF_SAMPLE ? nlist : CF_SAMPLE;
+    const int stride = nlist / m;
     const unsigned pool_cap = (unsigned)((size_t)n_q * CS_CAND);
-    if (listmask) (void)hipMemsetAsync(listmask, 0, (size_t)nlist * mask_words * 4, st);       // (NULL: the caller walks probe_out only)
-    (void)hipMemsetAsync(small, 0, b_small, st);
+    if (a.listmask) (void)hipMemsetAsync(a.listmask, 0, (size_t)nlist * a.mask_words * 4, st);       // (NULL: the caller walks probe_out only)
+    (void)hipMemsetAsync(cnt, 0, sizeof *cnt, st);
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cus <= 0 || cus > 256) cus = 256;           // (the wave statistics hold 256 CUs)
     const size_t lds128 = (size_t)2 * CG_LISTS * (CF_K + 8) * 2;
     const size_t lds_v3 = (size_t)2 * CG_QROWS * (CF_K + 8) * 2 + (size_t)CF_HIT_CAP * 10;
-    static std::atomic<bool> attr[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)dph_coarse_filter_gemm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dph_coarse_filter_gemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dph_coarse_filter_gemm_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dph_coarse_filter_gemm2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_v3);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dph_coarse_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)2 * CS_CAND * 4));
-        if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(coarse filter kernels): %s\n", hipGetErrorString(e));
-        if (dev >= 0 && dev < 64) attr[dev] = e == hipSuccess;
-    }
+    CG_ALLOW_LDS(dph_coarse_filter_gemm_kernel<true>, lds128, dev);
+    CG_ALLOW_LDS(dph_coarse_filter_gemm_kernel<false>, lds128, dev);
+    CG_ALLOW_LDS((dph_coarse_filter_gemm_kernel<false, true>), lds128, dev);
+    CG_ALLOW_LDS(dph_coarse_filter_gemm2_kernel, lds_v3, dev);
+    cs_select_allow_lds(dev);
     const int qt = (n_q + CG_QROWS - 1) / CG_QROWS;
-    const int np = nprobe < nlist ? nprobe : nlist;
+    const int np = a.nprobe < nlist ? a.nprobe : nlist;
     // enough candidates for the nprobe lists, the error band below them and the sampling noise; never more than the lists there are
     int target = 4 * np + 64;
     if (target > nlist) target = nlist;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const int tiles_s = (m + CG_LISTS - 1) / CG_LISTS, tiles_f = (nlist + CG_LISTS - 1) / CG_LISTS;
     // persistent: two workgroups per CU share the list tiles (fewer when the pass has several query tiles: grid.y)
     const int wg = std::max(1, 2 * cus / qt);
-    hipLaunchKernelGGL(dph_coarse_filter_gemm_kernel<true>, dim3(std::min(tiles_s, wg), qt), dim3(256), lds128, st, n_q, m, stride, (int64_t)tiles_f, c_hi, x_hi,
-                       sample, (const unsigned*)nullptr, (uint2*)nullptr, (unsigned short*)nullptr, (unsigned*)nullptr, 0u, (unsigned*)nullptr);
-    hipLaunchKernelGGL(dph_coarse_estimate_sample_kernel, dim3(n_q), dim3(CS_THREADS), 0, st, sample, n_q, m, stride, target, est);
+    hipLaunchKernelGGL(dph_coarse_filter_gemm_kernel<true>, dim3(std::min(tiles_s, wg), qt), dim3(256), lds128, st, n_q, m, stride, (int64_t)tiles_f, a.c_hi, a.x_hi,
+                       f.sample.p, (const unsigned*)nullptr, (uint2*)nullptr, (unsigned short*)nullptr, (unsigned*)nullptr, 0u, (unsigned*)nullptr);
+    hipLaunchKernelGGL(dph_coarse_estimate_sample_kernel, dim3(n_q), dim3(CS_THREADS), 0, st, f.sample.p, n_q, m, stride, target, est);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto bracket_begin = [&]() { ev0 = ev1 = nullptr; if (prof.next) { prof.next(prof.ctx, &ev0, &ev1); (void)hipEventRecord(ev0, st); } };
+    auto bracket_begin = [&]() { ev0 = ev1 = nullptr; if (a.prof.next) { a.prof.next(a.prof.ctx, &ev0, &ev1); (void)hipEventRecord(ev0, st); } };
     auto bracket_end = [&]() { if (ev1) (void)hipEventRecord(ev1, st); };
-    if (!(variant == 5 && c_pieces)) bracket_begin();
-    if (variant == 5 && c_pieces) {
+    const bool scan = a.variant == 5 && a.c_pieces;
+    if (!scan) bracket_begin();
+    if (scan) {
         // 128 query rows per read of the centroid image (one group of 32 per scan wave); a pass of more rows reads it once per 128 --
-        // 4 x 0.27 ms against the GEMM's 1.36 ms at 512 rows
-        char* sb = base + ((b_sample + b_pool_lk + b_pool_q + b_cand + b_small + 255) / 256) * 256;
-        uint2* pairs = (uint2*)sb;
-        unsigned* chunk_fill = (unsigned*)(sb + b_pairs);
-        unsigned* wave_counts = (unsigned*)(sb + b_pairs + b_fill);
-        int* counters = (int*)(sb + b_pairs + b_fill + b_wc);
-        uint4* qfrag = (uint4*)(sb + b_pairs + b_fill + b_wc + b_cnt);
-        // more than 128 rows: ONE launch of teams (dph_scan.hip MODE 4) -- the groups of 128 rows share every tile through the XCDs' L2
+        // 4 x 0.27 ms against the GEMM's 1.36 ms at 512 rows.
+        // More than 128 rows: ONE launch of teams (dph_scan.hip MODE 4) -- the groups of 128 rows share every tile through the XCDs' L2
         // instead of each reading the image from HBM.  Groups rounded up to a power of two that divides the 32 workgroups of an XCD.
         int n_groups = 1;
         while (n_groups * (int)DPH_QROWS < n_q) n_groups *= 2;
-        static const int teams_env = getenv("DPH_CF_TEAMS") ? atoi(getenv("DPH_CF_TEAMS")) : -1;     // (-1: the handle's setting)
-        const bool teams = (teams_env >= 0 ? teams_env != 0 : coarse_teams != 0) && n_groups >= 2 && n_groups <= 8 && cus_scan % (8 * n_groups) == 0;
+        const bool teams = a.teams != 0 && n_groups >= 2 && n_groups <= 8 && cus % (8 * n_groups) == 0;
         if (teams) {
-            hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((n_groups * 4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, x_hi, n_q, qfrag, n_groups);
+            hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((n_groups * 4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi, n_q, f.qfrag.p, n_groups);
             bracket_begin();
-            dph_launch_coarse_scan_teams(c_pieces, nlist, qfrag, n_q, n_groups, est, pairs, chunk_fill, wave_counts, counters, cus_scan, st);
+            dph_launch_coarse_scan_teams(a.c_pieces, nlist, f.qfrag, n_q, n_groups, est, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st);
             bracket_end();
-            hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)pairs, (const unsigned*)chunk_fill, (const int*)counters,
-                               n_q, 0u, cand, cand_cnt, (int)CS_CAND, pool_count, fail);
+            hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
+                               n_q, 0u, f.cand.p, cand_cnt, (int)CS_CAND, pool_count, fail);
         }
         for (int q0 = 0; !teams && q0 < n_q; q0 += DPH_QROWS) {
             const int nq = std::min(n_q - q0, (int)DPH_QROWS);
-            hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, x_hi + (int64_t)q0 * DPH_DIM, nq, qfrag);
+            hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi + (int64_t)q0 * DPH_DIM, nq, f.qfrag.p);
             bracket_begin();
-            dph_launch_coarse_scan(c_pieces, nlist, qfrag, nq, est + q0, pairs, chunk_fill, wave_counts, counters, cus_scan, st);
+            dph_launch_coarse_scan(a.c_pieces, nlist, f.qfrag, nq, est + q0, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st);
             bracket_end();
             // straight into the per-row candidate lists; DPH_CF_KEEP_POOL=1 (tools/debug_coarse_scan.py) writes the linear pool of the GEMM forms too
             static const bool keep_pool = getenv("DPH_CF_KEEP_POOL") && atoi(getenv("DPH_CF_KEEP_POOL")) != 0;
             if (keep_pool)
-                hipLaunchKernelGGL(dph_cf_flatten_kernel, dim3(256), dim3(256), 0, st, (const uint2*)pairs, (const unsigned*)chunk_fill, (const int*)counters,
-                                   pool_lk, pool_q, pool_count, pool_cap, fail, (unsigned)q0);
-            hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)pairs, (const unsigned*)chunk_fill, (const int*)counters,
-                               n_q, (unsigned)q0, cand, cand_cnt, (int)CS_CAND, keep_pool ? fail + 2 : pool_count, fail);
+                hipLaunchKernelGGL(dph_cf_flatten_kernel, dim3(256), dim3(256), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
+                                   f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail, (unsigned)q0);
+            hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
+                               n_q, (unsigned)q0, f.cand.p, cand_cnt, (int)CS_CAND, keep_pool ? &cnt->sink : pool_count, fail);
         }
-    } else if (variant >= 3 && c_frag)
+    } else if (a.variant >= 3 && a.c_frag)
         hipLaunchKernelGGL(dph_coarse_filter_gemm2_kernel, dim3(std::min((nlist + CF2_LISTS - 1) / CF2_LISTS, std::max(1, cus / qt)), qt), dim3(CF2_THREADS), lds_v3, st,
-                           n_q, nlist, c_frag, x_hi, est, pool_lk, pool_q, pool_count, pool_cap, fail, variant == 4 ? 1 : 0);
-    else if (variant >= 2)
-        hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, true>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, c_hi, x_hi,
-                           (float*)nullptr, est, pool_lk, pool_q, pool_count, pool_cap, fail);
+                           n_q, nlist, a.c_frag, a.x_hi, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail, a.variant == 4 ? 1 : 0);
+    else if (a.variant >= 2)
+        hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, true>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
+                           (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
     else
-        hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, false>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, c_hi, x_hi,
-                           (float*)nullptr, est, pool_lk, pool_q, pool_count, pool_cap, fail);
-    if (!(variant == 5 && c_pieces)) bracket_end();
-    if (!(variant == 5 && c_pieces))
-        hipLaunchKernelGGL(dph_coarse_bucket_kernel, dim3(64), dim3(CB_THREADS), 0, st, pool_lk, pool_q, pool_count, pool_cap, n_q, cand, cand_cnt, (int)CS_CAND);
-    hipLaunchKernelGGL(dph_coarse_select_kernel, dim3(n_q), dim3(CS_THREADS), (size_t)2 * CS_CAND * 4, st, x_dev, 0, n_q, (const int*)nullptr, 0, centroids,
-                       (const float*)nullptr, nlist, nprobe, cnorm_max, listmask, mask_words, probe_out, probe_stride, 1.02 * CF_HI_ERR,
-                       (const uint2*)cand, (const unsigned*)cand_cnt, (const unsigned*)est, fail, (unsigned*)nullptr, cnorm, cnorm_cap);
-    hipLaunchKernelGGL(dph_coarse_gate_kernel, dim3(1), dim3(64), 0, st, fail, n_q, gate);
+        hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, false>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
+                           (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
+    if (!scan) {
+        bracket_end();
+        hipLaunchKernelGGL(dph_coarse_bucket_kernel, dim3(64), dim3(CB_THREADS), 0, st, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, n_q, f.cand.p, cand_cnt, (int)CS_CAND);
+    }
+    hipLaunchKernelGGL(dph_coarse_select_kernel, dim3(n_q), dim3(CS_THREADS), CS_LDS, st, a.x, 0, n_q, (const int*)nullptr, 0, a.centroids,
+                       (const float*)nullptr, nlist, a.nprobe, a.cnorm_max, a.listmask, a.mask_words, a.probe_out, a.probe_stride, 1.02 * CF_HI_ERR,
+                       (const uint2*)f.cand, (const unsigned*)cand_cnt, (const unsigned*)est, fail, (unsigned*)nullptr, a.cnorm, a.cnorm_cap);
+    hipLaunchKernelGGL(dph_coarse_gate_kernel, dim3(1), dim3(64), 0, st, fail, n_q, &cnt->gate);
     // fail-over: the whole pass again through the bf16x3 chain, gated on the device (empty launches when nothing failed); it ORs into
     // the masks the filter form has set (a row that succeeded marks the same lists again) and rewrites the probe lists it covers
-    dph_launch_coarse_presplit(x_dev, 0, n_q, gate, 0, centroids, nlist, nprobe, cnorm_max, scores, listmask, mask_words, nullptr, 0, nullptr,
-                               probe_out, probe_stride, c_pk, x_pk, cs_slot, st, false, row_fail);
+    chain.gate = &cnt->gate;
+    chain.clear_mask = false;
+    dph_launch_coarse(chain, s, st);
 }
 
 // what the filter form did in the last pass over this scratch: out[0] = 1 when the pass failed over to the bf16x3 chain, out[1] = triples
 // its GEMM epilogue put into the pool (synchronises the device)
-int dph_coarse_filter_debug(void* cf_slot, unsigned out[2]) {
-    if (!cf_slot) { out[0] = out[1] = 0xFFFFFFFFu; return 0; }
-    const size_t off = (size_t)DPH_PASS_MAX * CF_SAMPLE * 4 + (size_t)DPH_PASS_MAX * CS_CAND * 8 + (size_t)DPH_PASS_MAX * CS_CAND * 2 +
-                       (size_t)DPH_PASS_MAX * CS_CAND * 8 + (size_t)2 * DPH_PASS_MAX * 4;
-    unsigned v[2] = {0, 0};
-    if (hipMemcpy(v, (char*)cf_slot + off, 8, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    out[0] = v[1];          // fail
-    out[1] = v[0];          // pool_count
-    return 0;
+int dph_coarse_filter_debug(const dph_coarse_scratch& s, unsigned out[2]) {
+    const dph_coarse_counters* const cnt = s.filter.cnt;
+    if (!cnt) { out[0] = out[1] = 0xFFFFFFFFu; return 0; }
+    return hipMemcpy(&out[0], &cnt->fail, 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&out[1], &cnt->pool_count, 4, hipMemcpyDeviceToHost) != hipSuccess;
 }
 
 // the candidate pool the filter left behind: (list, key) and query row of up to `cap` triples; returns the pool count (-1: copy failed)
-long long dph_coarse_filter_debug_pool(void* cf_slot, unsigned* lk_host, unsigned short* q_host, long long cap) {
-    if (!cf_slot) return 0;
-    const size_t o_lk = (size_t)DPH_PASS_MAX * CF_SAMPLE * 4, o_q = o_lk + (size_t)DPH_PASS_MAX * CS_CAND * 8,
-                 o_cnt = o_q + (size_t)DPH_PASS_MAX * CS_CAND * 2 + (size_t)DPH_PASS_MAX * CS_CAND * 8 + (size_t)2 * DPH_PASS_MAX * 4;
+long long dph_coarse_filter_debug_pool(const dph_coarse_scratch& s, unsigned* lk_host, unsigned short* q_host, long long cap) {
+    const dph_coarse_scratch::filter_part& f = s.filter;
+    if (!f.cnt) return 0;
     unsigned n = 0;
-    if (hipMemcpy(&n, (char*)cf_slot + o_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(&n, &f.cnt.p->pool_count, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     const long long m = (long long)n < cap ? (long long)n : cap;
     if (m > 0) {
-        if (hipMemcpy(lk_host, (char*)cf_slot + o_lk, (size_t)m * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        if (hipMemcpy(q_host, (char*)cf_slot + o_q, (size_t)m * 2, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (hipMemcpy(lk_host, f.pool_lk, (size_t)m * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (hipMemcpy(q_host, f.pool_q, (size_t)m * 2, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     }
     return (long long)n;
 }
@@ -1567,10 +1510,9 @@ __global__ __launch_bounds__(256) void dph_units_gather_kernel(const int* __rest
 }
 
 void dph_launch_units_build(const unsigned* listmask, int nlist, const int* list_tile0, const int8_t* q1, int q0,
-                            int chunk_cap, int unit_cap, int* unit_counts, int* unit_next, int* slot_q, int4* unit_recs,
-                            int4* unit_list_recs, int8_t* unit_frags, int2* unit_offsets, int spread, hipStream_t st, bool x16) {
-    // unit_counts[4] and unit_next[DPH_UNIT_LAUNCHES] are one allocation
-    (void)unit_next;
+                            int chunk_cap, int unit_cap, int* unit_counts, int* slot_q, int4* unit_recs, int4* unit_list_recs,
+                            int8_t* unit_frags, int2* unit_offsets, int spread, hipStream_t st, bool x16) {
+    // unit_counts[4] and the DPH_UNIT_LAUNCHES work-queue heads behind it are one allocation
     (void)hipMemsetAsync(unit_counts, 0, (size_t)(4 + DPH_UNIT_LAUNCHES) * sizeof(int), st);
     hipLaunchKernelGGL(dph_units_offsets_kernel, dim3(1), dim3(UO_THREADS), 0, st, listmask, nlist, list_tile0, unit_offsets,
                        unit_counts);

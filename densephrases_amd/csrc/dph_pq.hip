@@ -912,11 +912,9 @@ struct dph_pq {
     std::vector<int64_t> h_top_prefix;                     // [i] = codes in the i longest lists: what a row can meet at most with nprobe = i
     // what lives until the index is freed
     dev_buf<float> qrot; int64_t qrot_rows = 0;            // rotated query halves of dph_pq_window
-    void* coarse_cs = nullptr;                             // candidate scratch of the one-pass probe selection (allocated by dph_launch_coarse_presplit)
-    void* coarse_cf = nullptr;                             // scratch of the filter form (allocated by dph_launch_coarse_filter)
+    dph_coarse_scratch coarse;                             // of the coarse quantizer (dph_launch_coarse / dph_launch_coarse_filter allocate what they need)
     dev_buf<unsigned long long> phase_prof;                // dph_debug_pq_phases: [workgroups][8], allocated by the first call
     int phase_wgs = 0;
-    ~dph_pq() { if (coarse_cs) (void)hipFree(coarse_cs); if (coarse_cf) (void)hipFree(coarse_cf); }
 };
 
 int dph_pq_alloc(dph_pq** out, int device, int64_t ntotal, int nlist, int M) {
@@ -945,13 +943,13 @@ int dph_pq_coarse_debug(dph_pq* p, unsigned out[2]) {
     if (!p) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipDeviceSynchronize());
-    return dph_coarse_filter_debug(p->coarse_cf, out) ? fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
+    return dph_coarse_filter_debug(p->coarse, out) ? fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
 }
 int dph_pq_coarse_debug_pool(dph_pq* p, unsigned* lk_host, unsigned short* q_host, long long cap, long long* count) {
     if (!p || !count) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipDeviceSynchronize());
-    *count = dph_coarse_filter_debug_pool(p->coarse_cf, lk_host, q_host, cap);
+    *count = dph_coarse_filter_debug_pool(p->coarse, lk_host, q_host, cap);
     return *count < 0 ? fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
 }
 // what the LAST pass left in the scan's bookkeeping: info[8] = {counters[0..3] (pairs, next, units, -), cand_cap, unit_cap, pair_cap, rows of
@@ -1253,26 +1251,33 @@ int dph_pq_search_dev(dph_pq* p, const float* x_dev, int64_t n, int k, int nprob
         HIPCHK(hipMemsetAsync(p->s.counters, 0, 64 + (size_t)3 * p->s.cap_rows * 4, st));      // counters, bounds, candidate counts, overflow flags (the coarse
                                                                                           // quantizer flags a row whose error band overflows there too)
         unsigned* const lmask = by_rows ? nullptr : p->s.listmask;       // the row-major scan walks the probe lists, not the masks (134 MB to clear at 2^20 lists)
+        dph_coarse_filter_args c;
+        c.x = p->s.xp; c.n_q = nq;
+        c.centroids = p->cent; c.nlist = p->nlist; c.nprobe = nprobe; c.cnorm_max = p->cnorm_max;
+        c.scores = p->s.scores;
+        c.listmask = lmask; c.mask_words = DPH_UNIT_WORDS;
+        c.probe_out = by_rows ? p->s.probe.p : nullptr; c.probe_stride = nprobe;
+        c.c_pk = p->cent_pk; c.x_pk = p->cent_pk ? p->s.xp_pk.p : nullptr;
+        c.row_fail = p->s.overflow;
         if (p->cent_hi && p->coarse_filter) {
+            c.c_hi = p->cent_hi; c.x_hi = p->s.xp_hi; c.c_frag = p->cent_frag; c.c_pieces = p->cent_pieces;
+            c.cnorm = p->cnorm; c.cnorm_cap = p->cnorm_cap;
+            c.variant = p->coarse_filter; c.teams = p->coarse_teams;
             // profiling: an event pair of its own around EVERY launch of the filter's dominant kernel (the scan; the GEMM forms: the one
             // GEMM launch) -- what a rocprofv3 kernel trace reports per dispatch, so the two can be held against each other
-            dph_event_source src{nullptr, nullptr};
             if (p->profile) {
-                src.ctx = p;
-                src.next = [](void* ctx, hipEvent_t* a, hipEvent_t* b) {
+                c.prof.ctx = p;
+                c.prof.next = [](void* ctx, hipEvent_t* a, hipEvent_t* b) {
                     dph_pq* q = (dph_pq*)ctx;
                     const std::pair<hipEvent_t, hipEvent_t> ev = q->prof_free.take();
                     q->prof_events.v.push_back(ev);
                     *a = ev.first; *b = ev.second;
                 };
             }
-            dph_launch_coarse_filter(p->s.xp, nq, p->cent, p->cent_hi, p->s.xp_hi, p->cent_pk, p->s.xp_pk, p->nlist, nprobe, p->cnorm_max, p->s.scores, lmask,
-                                     DPH_UNIT_WORDS, by_rows ? p->s.probe : nullptr, nprobe, &p->coarse_cs, &p->coarse_cf, st, src, p->s.overflow, p->coarse_filter, p->cent_frag, p->cent_pieces, p->cnorm, p->cnorm_cap, p->coarse_teams);
+            dph_launch_coarse_filter(c, p->coarse, st);
         }
         else
-            dph_launch_coarse_presplit(p->s.xp, 0, nq, nullptr, 0, p->cent, p->nlist, nprobe, p->cnorm_max, p->s.scores, lmask, DPH_UNIT_WORDS,
-                                       nullptr, 0, nullptr, by_rows ? p->s.probe : nullptr, nprobe, p->cent_pk, p->cent_pk ? p->s.xp_pk : nullptr, &p->coarse_cs, st,
-                                       true, p->s.overflow);
+            dph_launch_coarse(c, p->coarse, st);
         pq_scan_args a;
         a.xp = p->s.xp; a.cent = p->cent; a.lut = p->s.lut; a.codes = p->codes; a.list_off = p->list_off;
         a.pairs = p->s.pairs; a.n_pairs = p->s.counters + 0; a.next = p->s.counters + 1; a.pair_cap = p->pair_cap;
