@@ -95,6 +95,21 @@ struct dph_tuning {
     int side_grid = 0;                   // tuning key "side_grid": scan workgroups of the prepare stage's sampled levels (0 = grid)
 };
 
+// The device counters of a search call, in the order the chain fills them.  A PQ index counts its rows' statuses into words of its own.
+struct dph_search_counters {
+    int fail_first;                      // rows failing the first attempt (the gate of the retry passes)
+    int fail_retry;                      // rows failing the retry = rows of the fp64 fallback (its gate)
+    int unsettled;                       // rows still flagged 1 at the end of the chain
+    int reselect;                        // rows the in-pass wide re-select certified (no re-scan)
+    int nonfinite;                       // non-finite query rows of the call
+    struct { int uncertified, nonfinite; } pq;       // PQ index: what dph_launch_count_status counts (out[0], out[1])
+    int spare;
+};
+static_assert(sizeof(dph_search_counters) == 32 && offsetof(dph_search_counters, nonfinite) == offsetof(dph_search_counters, reselect) + sizeof(int),
+              "search_core clears reselect and nonfinite with one memset");
+// the bound a pass's full scan runs under, and the stride of the last ladder level that ran under a bound itself (0 = none: nothing to fuse)
+struct pass_bound { const int* tau = nullptr; int fuse_stride = 0; };
+
 struct dph_scratch {
     int64_t cap_rows = 0;                // query rows the per-call scratch is sized for
     struct qimg { dev_buf<float> x; dev_buf<int8_t> frag, q1, q2; dev_buf<dph_qinfo> qinfo; dev_buf<int> lmax; dev_buf<int8_t> qaux;
@@ -105,41 +120,26 @@ struct dph_scratch {
     int cap_k = 0;
     dev_buf<int32_t> ik_dev, fail_dev, fail2_dev, retry_rows, exact_rows;
     dev_buf<int> retry_tau;
-    dev_buf<int> counters;               // [0] rows failing the first attempt, [1] failing the retry, [2..3] spare
+    dev_buf<dph_search_counters> counters;       // [1]
     dev_buf<float> exact_x;
     dev_buf<char> exact_scratch;         // hit buffers of the fp64 fallback (its .n: their size in bytes)
     // per-pass scratch (fixed size)
     dev_buf<uint2> pairs; dev_buf<unsigned> chunk_fill, wave_counts; dev_buf<uint64_t> buckets;
-    dev_buf<unsigned> counts_raw;        // work-queue head | bucket counts | overflow flags ...
-    unsigned* bucket_counts = nullptr;   // ... and where the bucket counts start in it
-    dev_buf<int> tau_dev;                // [2][256] per-row bounds of the current pass (ladder ping-pong)
-    // IVF: what a pass writes (dph_index_set_ivf sizes it from the lists) ...
-    struct ivf_pass {
-        dev_buf<float> coarse_scores;    // [coarse_rows, nlist] fp32: query x centroid scores of the current pass
-        int coarse_rows = 0;
-        dev_buf<unsigned> listmask;      // [nlist][8]   bit j of word w: query row 32w+j of the pass probes the list
-        dev_buf<unsigned> tilemask;      // [n_tiles][8] the same per tile (what the scan reads)
-        dev_buf<int2> unit_offsets;      // [nlist] first chunk / first unit of every list in the current pass
-        dev_buf<unsigned> listmask_u;    // [nlist][DPH_UNIT_WORDS]
-        dev_buf<int> unit_counts;        // [4] chunks, units, error, spare + [DPH_UNIT_LAUNCHES] work-queue heads
-    } ivf;
-    // ... and the work queue of a unit-scan pass of up to DPH_PASS_MAX query rows (ensure_units sizes it from nprobe)
-    struct unit_queue {
-        dev_buf<int> slot_q; dev_buf<int4> unit_recs, unit_list_recs; dev_buf<int8_t> unit_frags;
-        int chunk_cap = 0, unit_cap = 0;
-    } uq;
+    dev_buf<dph_pass_counters> pass_cnt; // [1] work-queue head | bucket counts | overflow flags of the current pass
+    dev_buf<int> tau_dev;                // [2][DPH_PASS_MAX] per-row bounds of the current pass (ladder ping-pong)
+    dph_ivf_pass ivf;                    // IVF: what a pass writes (dph_index_set_ivf sizes it from the lists) ...
+    dph_unit_queue uq;                   // ... and the work queue of a unit-scan pass (ensure_units sizes it from nprobe)
     dph_coarse_scratch coarse;           // of the coarse quantizer (dph_launch_coarse allocates what it needs on first use)
     dev_buf<long long> kmeans_sums; int kmeans_nlist = 0;        // [nlist,768] integer sums of a k-means update
     dph_search_stats stats{};
     bool stats_pending = false;          // device counters of the last device-pointer call not read back yet
-    int64_t stats_rows = 0;
     // measurement hook: event pairs around scan launches
     bool profile = false;
     dph_event_pairs prof_events;         // around the full-scan launches
     dph_event_pairs prof_events_ladder;  // around the scan launches of the ladder levels
     dph_event_pairs prof_free;
     // the two-stage form of a search (dph_search_prepare_dev / dph_search_finish_dev): what the prepare stage left behind
-    struct prepared { bool valid = false; int64_t n = 0; int k = 0; const int* tau = nullptr; int fuse_stride = 0; int qb = 1; } prep;
+    struct prepared { bool valid = false; int64_t n = 0; int k = 0; pass_bound bound; } prep;
 };
 
 struct dph_index {
@@ -171,6 +171,14 @@ static void build_lut(dph_shard* s) {
 // the rows, metadata and shard constants of an index that has twins (or is one) are shared and stay as they are
 #define DPH_NOT_TWINNED(h, who) \
     do { if ((h) && ((h)->twin_of || (h)->n_twins > 0)) return fail(DPH_E_STATE, std::string(who) + ": not on an index that has twins or is one"); } while (0)
+
+// the profile bracket of a scan launch: a (start, stop) event pair around it, kept in `list` until dph_profile_read* drains it
+template <typename Launch> static void bracketed(dph_index* h, bool on, dph_event_pairs& list, hipStream_t st, Launch launch) {
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    if (on) { ev = h->sc.prof_free.take(); (void)hipEventRecord(ev.first, st); }
+    launch();
+    if (on) { (void)hipEventRecord(ev.second, st); list.v.push_back(ev); }
+}
 
 extern "C" {
 
@@ -656,7 +664,7 @@ int dph_index_set_ivf(dph_index* h, int nlist, const float* centroids, const int
         if (tile_list[t] < 0 || tile_list[t] >= nlist) return fail(DPH_E_ARG, "dph_index_set_ivf: tile_list out of range");
     HIPCHK(hipSetDevice(h->device));
     h->sh->centroids.reset(); h->sh->tile_list.reset(); h->sh->list_tile0.reset();
-    h->sc.ivf = dph_scratch::ivf_pass(); h->sc.uq = dph_scratch::unit_queue();
+    h->sc.ivf = dph_ivf_pass(); h->sc.uq = dph_unit_queue();
     // the unit scan needs every list to be one contiguous run of tiles (what ivf.build_list_major writes)
     std::vector<int> tile0((size_t)nlist + 1, 0);
     h->sh->lists_contiguous = nlist <= 65536 && h->sh->n_tiles < (int64_t)0x7fffffff;
@@ -685,7 +693,7 @@ int dph_index_set_ivf(dph_index* h, int nlist, const float* centroids, const int
         HIPCHK(hipMemcpy(h->sh->list_tile0, tile0.data(), ((size_t)nlist + 1) * 4, hipMemcpyHostToDevice));
         HIPCHK(h->sc.ivf.listmask_u.alloc((size_t)nlist * DPH_UNIT_WORDS));
         HIPCHK(h->sc.ivf.unit_offsets.alloc((size_t)nlist));
-        HIPCHK(h->sc.ivf.unit_counts.alloc((size_t)(4 + DPH_UNIT_LAUNCHES)));
+        HIPCHK(h->sc.ivf.unit_cnt.alloc(1));
     }
     HIPCHK(h->sh->centroids.alloc((size_t)nlist * DPH_DIM));
     HIPCHK(hipMemcpy(h->sh->centroids, centroids, (size_t)nlist * DPH_DIM * 4, hipMemcpyHostToDevice));
@@ -943,14 +951,11 @@ static int ensure_scratch(dph_index* h, int64_t n, int k_host) {
         // two images: [0] the passes of the first attempt (what dph_scan_counters reports), [1] the retry passes
         HIPCHK(h->sc.wave_counts.alloc((size_t)2 * h->tune.grid * 4 * 2));
         HIPCHK(h->sc.buckets.alloc((size_t)DPH_PASS_MAX * DPH_BUCKET_CAP));
-        // [4] work-queue head of the scan, chunks claimed from the pair pool (+ padding) | [DPH_PASS_MAX] bucket counts |
-        // [DPH_PASS_MAX] overflow flags: one allocation, cleared by one memset in front of every scan (dph_clear_pass_counters)
-        HIPCHK(h->sc.counts_raw.alloc((size_t)(4 + 2 * DPH_PASS_MAX)));
-        HIPCHK(hipMemset(h->sc.counts_raw, 0, (size_t)(4 + 2 * DPH_PASS_MAX) * sizeof(unsigned)));
-        h->sc.bucket_counts = h->sc.counts_raw + 4;
+        HIPCHK(h->sc.pass_cnt.alloc(1));
+        HIPCHK(hipMemset(h->sc.pass_cnt, 0, sizeof(dph_pass_counters)));
         HIPCHK(h->sc.tau_dev.alloc((size_t)2 * DPH_PASS_MAX));
-        HIPCHK(h->sc.counters.alloc(8));          // [0..3] see the struct, [4] non-finite query rows of the call
-        HIPCHK(hipMemset(h->sc.counters, 0, 8 * sizeof(int)));
+        HIPCHK(h->sc.counters.alloc(1));
+        HIPCHK(hipMemset(h->sc.counters, 0, sizeof(dph_search_counters)));
         HIPCHK(h->sc.exact_x.alloc((size_t)DPH_EXACT_ROWS_DEV * DPH_DIM));
     }
     if (!h->sc.exact_scratch) {
@@ -1018,7 +1023,7 @@ static int ensure_units(dph_index* h, int nprobe) {
     const int64_t segs_max = (h->sh->max_list_tiles + DPH_UNIT_TILES - 1) / DPH_UNIT_TILES;
     const int64_t unit_cap = h->sh->total_segs + extra * std::max<int64_t>(1, segs_max);
     if (chunk_cap <= h->sc.uq.chunk_cap && unit_cap <= h->sc.uq.unit_cap) return DPH_OK;
-    h->sc.uq = dph_scratch::unit_queue();
+    h->sc.uq = dph_unit_queue();
     if (chunk_cap > (1 << 22) || unit_cap > (1 << 26)) return fail(DPH_E_ARG, "unit scan: work queue too large for this nprobe");
     HIPCHK(h->sc.uq.slot_q.alloc((size_t)chunk_cap * DPH_UNIT_SLOTS));
     HIPCHK(h->sc.uq.unit_recs.alloc((size_t)unit_cap));
@@ -1068,7 +1073,7 @@ static dph_idmap make_idmap(const dph_shard* s) {
 
 static dph_pass make_pass(dph_index* h, const dph_scratch::qimg& q, const float* x, int q0, int n_q, int qb) {
     dph_pass p{};
-    p.db = h->sh->db; p.n_rows = h->sh->n_rows; p.n_tiles = h->sh->n_tiles; p.id_base = h->sh->id_base; p.row_ids = h->sh->row_ids;
+    p.db = h->sh->db; p.n_rows = h->sh->n_rows; p.row_ids = h->sh->row_ids;
     p.idmap = make_idmap(h->sh);
     p.grid = h->tune.grid;
     p.qb = qb; p.q0 = q0; p.n_q = n_q; p.gate = nullptr; p.gate_base = 0;
@@ -1076,26 +1081,30 @@ static dph_pass make_pass(dph_index* h, const dph_scratch::qimg& q, const float*
     p.aux = h->sh->aux_lay.stride > 0 ? h->sh->aux : nullptr; p.aux_lay = h->sh->aux_lay; p.qaux = q.qaux;
     p.tilemask = nullptr;
     p.outliers = h->sh->outliers; p.n_out = h->sh->n_out;
-    p.pairs = h->sc.pairs; p.chunk_fill = h->sc.chunk_fill; p.wave_counts = h->sc.wave_counts; p.buckets = h->sc.buckets; p.bucket_counts = h->sc.bucket_counts;
-    p.overflow = h->sc.bucket_counts + DPH_PASS_MAX;
-    p.queue_head = (int*)h->sc.counts_raw.p; p.seg_tiles = h->tune.seg_tiles;
+    p.pairs = h->sc.pairs; p.chunk_fill = h->sc.chunk_fill; p.wave_counts = h->sc.wave_counts; p.buckets = h->sc.buckets; p.cnt = h->sc.pass_cnt;
+    p.seg_tiles = h->tune.seg_tiles;
     p.sched = h->tune.scan_sched[qb == 2 ? 1 : 0];
     return p;
 }
 
-// Sharded two-phase form (dph_search_sample_dev / dph_search_bounded_dev): `top_out` != NULL stops after the ladder and
-// returns the DPH_SAMPLE_KEEP best sampled scores per row; `tau_ext` != NULL skips the ladder and scans under the
-// caller's bounds, `bound_out` then receives the upper bound of the score of any row this shard did not return.
-struct search_opts {
-    int32_t* top_out = nullptr;
-    const int32_t* tau_ext = nullptr;
-    double* bound_out = nullptr;
-    int phase = 0;                       // two-stage form: 1 = quantise + sampled levels only (state kept in h->sc.prep), 2 = the rest
+// What a pass is asked for and where its results go: filled once per call (the entry points, search_core) and adjusted per pass.
+// The sharded two-phase form (dph_search_sample_dev / dph_search_bounded_dev): `top_out` != NULL stops after the ladder and returns
+// the DPH_SAMPLE_KEEP best sampled scores per row; `tau_ext` != NULL skips the ladder and scans under the caller's bounds,
+// `bound_out` then receives the upper bound of the score of any row this shard did not return.
+struct pass_args {
+    int k = 1, nprobe = 0;
+    int32_t* top_out = nullptr;          // [rows][DPH_SAMPLE_KEEP]
+    const int32_t* tau_ext = nullptr;    // [rows]: the kernels read entries < n_q only
+    const int* rowmap = nullptr;         // != NULL marks a retry pass: outputs scattered to rowmap[slot], larger C, failures go to fail2
+    float* D = nullptr; int64_t* I = nullptr; int32_t* status = nullptr; double* bound_out = nullptr;
+    int32_t* ik_out = nullptr; int32_t* fail_out = nullptr;
+    bool retry() const { return rowmap != nullptr; }
+    int C() const { return retry() ? DPH_SELECT_C_MAX : std::min(std::max(k + 32, 2 * k), DPH_SELECT_C_MAX); }   // candidates the select step re-scores
 };
+// the two-stage form cuts a first-attempt pass behind its ladder (dph_search_prepare_dev / dph_search_finish_dev)
+enum search_stage { SEARCH_WHOLE, SEARCH_PREPARE, SEARCH_FINISH };
 
-// one pass = 128*qb query rows: [probe masks] -> ladder of sampled bounds -> full filter scan -> refine -> select.
-// `rowmap` != NULL marks a retry pass (outputs scattered to rowmap[slot], larger C, failures go to fail2).
-// The full scan behind a FUSED finest ladder level of stride S (run_pass): that level scanned tiles 0, S, 2S, ...; the full scan
+// The full scan behind a FUSED finest ladder level of stride S (pass_scan_select): that level scanned tiles 0, S, 2S, ...; the full scan
 // visits the other `visit` tiles, visited index v -> tile v + v / (S - 1) + 1, and the kernel takes the quotient as
 // (v * m) >> 29 with m = ceil(2^29 / (S - 1)) (dph_scan.hip, tile_of).  With err = m (S - 1) - 2^29 that is exact as long as
 // v * err < 2^29 (the fraction the multiply adds stays below 1 / (S - 1)).  Returns the number of tiles to visit and the
@@ -1122,28 +1131,26 @@ static dph_coarse_args coarse_args(const dph_shard& sh, const float* x, int q0, 
     return c;
 }
 
-static int run_pass(dph_index* h, dph_pass p, int k, int nprobe, const int32_t* tau_ext, int32_t* top_out,
-                    const int* rowmap, float* D, int64_t* I, int32_t* status, double* bound_out, int32_t* ik_out,
-                    int32_t* fail_out, hipStream_t st, int phase = 0) {
-    const bool retry = rowmap != nullptr;
-    const bool units = !retry && !p.gate && use_units(h, nprobe);
+// One pass = 128*qb query rows (unit scan: up to DPH_PASS_MAX), three stages: pass_probe [probe masks] -> pass_ladder (sampled bounds)
+// -> pass_scan_select (full filter scan -> refine -> select).  search_core says which of them a pass runs.
+// Stage 1, the probe set-up of a pass over a list-major shard: coarse search -> probe masks, or -> the work queue of a unit scan.
+static int pass_probe(dph_index* h, dph_pass& p, const pass_args& a, hipStream_t st) {
     const dph_shard& sh = *h->sh;
-    dph_scratch::ivf_pass& ivf = h->sc.ivf;
-    if (units) {
-        int rc = ensure_units(h, nprobe);
+    dph_ivf_pass& ivf = h->sc.ivf;
+    if (!a.retry() && !p.gate && use_units(h, a.nprobe)) {
+        int rc = ensure_units(h, a.nprobe);
         if (rc) return rc;
-        const dph_scratch::unit_queue& uq = h->sc.uq;
-        dph_coarse_args c = coarse_args(sh, p.x, p.q0, p.n_q, nprobe, ivf.coarse_scores);
+        const dph_unit_queue& uq = h->sc.uq;
+        dph_coarse_args c = coarse_args(sh, p.x, p.q0, p.n_q, a.nprobe, ivf.coarse_scores);
         c.listmask = ivf.listmask_u; c.mask_words = DPH_UNIT_WORDS;
         dph_launch_coarse(c, h->sc.coarse, st);
-        dph_launch_units_build(ivf.listmask_u, sh.nlist, sh.list_tile0, p.q1, p.q0, uq.chunk_cap, uq.unit_cap, ivf.unit_counts,
-                               uq.slot_q, uq.unit_recs, uq.unit_list_recs, uq.unit_frags, ivf.unit_offsets, h->tune.ivf_spread, st, dph_frag_x16(sh.aux_lay.stride));
-        p.unit_recs = uq.unit_recs; p.unit_list_recs = uq.unit_list_recs; p.unit_counts = ivf.unit_counts; p.unit_next = ivf.unit_counts + 4; p.unit_launch = 0;
+        dph_launch_units_build(ivf, uq, sh.nlist, sh.list_tile0, p.q1, p.q0, h->tune.ivf_spread, dph_frag_x16(sh.aux_lay.stride), st);
+        p.unit_recs = uq.unit_recs; p.unit_list_recs = uq.unit_list_recs; p.unit_cnt = ivf.unit_cnt; p.unit_launch = 0;
         p.slot_q = uq.slot_q; p.unit_frags = uq.unit_frags; p.listmask = ivf.listmask_u; p.tile_list = sh.tile_list;
         p.mask_words = DPH_UNIT_WORDS;
     } else if (sh.row_ids) {
-        if (nprobe > 0) {
-            dph_coarse_args c = coarse_args(sh, p.x, p.q0, p.n_q, nprobe, ivf.coarse_scores);
+        if (a.nprobe > 0) {
+            dph_coarse_args c = coarse_args(sh, p.x, p.q0, p.n_q, a.nprobe, ivf.coarse_scores);
             c.gate = p.gate; c.gate_base = p.gate_base;
             c.listmask = ivf.listmask; c.mask_words = 8; c.tilemask = ivf.tilemask;
             dph_launch_coarse(c, h->sc.coarse, st);
@@ -1152,106 +1159,83 @@ static int run_pass(dph_index* h, dph_pass p, int k, int nprobe, const int32_t* 
             p.tilemask = sh.onesmask;
         }
     }
-    int C = k + 32;
-    if (C < 2 * k) C = 2 * k;
-    if (retry) C = DPH_SELECT_C_MAX;
-    if (C > DPH_SELECT_C_MAX) C = DPH_SELECT_C_MAX;
-    const int nset = 4;
-    const int* tau = nullptr;
-    int fuse_stride = 0;                     // stride of the last ladder level this pass ran itself (0 = none)
-    if (phase == 2) {
-        tau = h->sc.prep.tau;                   // the prepare stage's last bound; its finest level's candidates wait in the buckets
-        fuse_stride = h->sc.prep.fuse_stride;
-    } else if (tau_ext) {
-        tau = tau_ext;                       // [rows of the pass]: the kernels read entries < n_q only
+    return DPH_OK;
+}
+
+// Stage 2, the ladder of sampled bounds (`p` by value: the unit work-queue head moves with the levels).  The sample form
+// (a.top_out) gets the best sampled scores of the last level.
+static int pass_ladder(dph_index* h, dph_pass p, const pass_args& a, hipStream_t st, pass_bound* b) {
+    const bool units = p.unit_recs != nullptr;
+    std::vector<ladder_level> levels;
+    double last_ratio = 1.0;             // rows of the shard (of the probed lists) per row of the last level's sample
+    if (units) {
+        build_ladder_units(h, p.n_q, a.nprobe, levels, &last_ratio);
     } else {
-        // (prepare stage: the sampled levels run on the few CUs of a side stream -- as many workgroups as those, not one per CU of the chip)
-        if (phase == 1 && h->tune.side_grid > 0) p.grid = std::min(h->tune.side_grid, h->tune.grid);
-        std::vector<ladder_level> levels;
-        double last_ratio = 1.0;             // rows of the shard (of the probed lists) per row of the last level's sample
-        if (units) {
-            build_ladder_units(h, p.n_q, nprobe, levels, &last_ratio);
-        } else {
-            std::vector<int> strides;
-            build_ladder(h, p.qb, strides);
-            for (int v : strides) levels.push_back({v, 0xFFFFu});
-            if (!strides.empty()) last_ratio = strides.back();
-        }
-        // the bound of a level is its kp-th best sampled score: ~kp * last_ratio rows beat it in the full scan, and
-        // that must cover the C candidates the select step wants to re-score
-        int kp = h->tune.sample_kp;
-        if (!levels.empty()) {
-            const int need = (int)((double)C * 1.5 / last_ratio) + 8;
-            if (need > kp) kp = need;
-        }
-        if ((int)levels.size() + 1 > DPH_UNIT_LAUNCHES) return fail(DPH_E_STATE, "ladder deeper than the unit work-queue heads");
-        for (size_t i = 0; i < levels.size(); ++i) {
-            const int64_t tiles = (h->sh->n_tiles + levels[i].stride - 1) / levels[i].stride;
-            int* out = h->sc.tau_dev + (i & 1) * DPH_PASS_MAX;
-            // a level that ran under a bound leaves a small bucket the full scan can build on; a COLD level (no bound: every
-            // sampled row is in its bucket, more than the select step sorts) cannot be fused
-            const bool bounded_level = tau != nullptr;
-            std::pair<hipEvent_t, hipEvent_t> lev{nullptr, nullptr};
-            if (h->sc.profile && !retry) {
-                lev = h->sc.prof_free.take();
-                (void)hipEventRecord(lev.first, st);
-            }
-            if (units) { p.unit_launch = (int)i; dph_launch_scan_units(p, true, levels[i].stride, levels[i].rowmask, tau, st); }
-            else dph_launch_scan(p, true, tiles, levels[i].stride, tau, nset, st);
-            if (h->sc.profile && !retry) { (void)hipEventRecord(lev.second, st); h->sc.prof_events_ladder.v.push_back(lev); }
-            dph_launch_refine(p, st);
-            int* top = (top_out && i + 1 == levels.size()) ? top_out : nullptr;
-            dph_launch_threshold(p, kp, tau, out, top, st);
-            tau = out;
-            fuse_stride = bounded_level ? levels[i].stride : 0;
-        }
-        if (phase == 1) {
-            h->sc.prep.tau = tau;
-            h->sc.prep.fuse_stride = fuse_stride;
-            return DPH_OK;
-        }
-        if (top_out) {
-            // a shard too small for any ladder level shares nothing (INT_MIN everywhere)
-            if (levels.empty())
-                HIPCHK(hipMemsetD32Async((hipDeviceptr_t)top_out, (int)0x80000000, (size_t)p.n_q * DPH_SAMPLE_KEEP, st));
-            return DPH_OK;
-        }
+        std::vector<int> strides;
+        build_ladder(h, p.qb, strides);
+        for (int v : strides) levels.push_back({v, 0xFFFFu});
+        if (!strides.empty()) last_ratio = strides.back();
     }
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (h->sc.profile && !retry) {
-        ev = h->sc.prof_free.take();
-        (void)hipEventRecord(ev.first, st);
+    // the bound of a level is its kp-th best sampled score: ~kp * last_ratio rows beat it in the full scan, and
+    // that must cover the C candidates the select step wants to re-score
+    int kp = h->tune.sample_kp;
+    if (!levels.empty()) kp = std::max(kp, (int)((double)a.C() * 1.5 / last_ratio) + 8);
+    if ((int)levels.size() + 1 > DPH_UNIT_LAUNCHES) return fail(DPH_E_STATE, "ladder deeper than the unit work-queue heads");
+    *b = pass_bound();
+    for (size_t i = 0; i < levels.size(); ++i) {
+        const int stride = levels[i].stride;
+        const int* tau = b->tau;
+        bracketed(h, h->sc.profile && !a.retry(), h->sc.prof_events_ladder, st, [&] {
+            if (units) { p.unit_launch = (int)i; dph_launch_scan_units(p, true, stride, levels[i].rowmask, tau, st); }
+            else dph_launch_scan(p, true, (h->sh->n_tiles + stride - 1) / stride, stride, tau, st);
+        });
+        dph_launch_refine(p, st);
+        int* out = h->sc.tau_dev + (i & 1) * DPH_PASS_MAX;
+        dph_launch_threshold(p, kp, tau, out, i + 1 == levels.size() ? a.top_out : nullptr, st);
+        // a level that ran under a bound leaves a small bucket the full scan can build on; a COLD level (no bound: every
+        // sampled row is in its bucket, more than the select step sorts) cannot be fused
+        b->fuse_stride = tau ? stride : 0;
+        b->tau = out;
     }
+    // a shard too small for any ladder level shares nothing (INT_MIN everywhere)
+    if (a.top_out && levels.empty()) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)a.top_out, (int)0x80000000, (size_t)p.n_q * DPH_SAMPLE_KEEP, st));
+    return DPH_OK;
+}
+
+// Stage 3: the full scan under b.tau, refine, select (+ the in-pass re-select).
+static int pass_scan_select(dph_index* h, dph_pass p, const pass_args& a, const pass_bound& b, hipStream_t st) {
+    const bool units = p.unit_recs != nullptr, retry = a.retry();
     // Fused finest level (flat shards): the last ladder level scanned every S-th tile under the previous level's bound, and its
     // refine left those tiles' candidates -- a superset of what the final bound admits -- in the buckets.  The full scan therefore
     // visits only the OTHER tiles and accumulates: the dump is read once per batch instead of 1 + 1/S times.  Every un-emitted row
-    // still has I <= tau: the fused tiles were filtered under a bound <= tau.
+    // still has I <= tau: the fused tiles were filtered under a bound <= tau.  (A pass that skipped the ladder brings stride 0.)
     int64_t full_tiles = h->sh->n_tiles;
-    if (!units && !h->sh->row_ids && !tau_ext && !retry && h->tune.ladder_fuse) {
+    if (!units && !h->sh->row_ids && h->tune.ladder_fuse) {
         unsigned m = 0;
-        const int64_t visit = fused_scan_plan(h->sh->n_tiles, fuse_stride, &m);
+        const int64_t visit = fused_scan_plan(h->sh->n_tiles, b.fuse_stride, &m);
         if (visit > 0) { p.skip_m = m; p.accumulate = true; full_tiles = visit; }
     }
-    if (!retry) h->sc.stats.fused_stride = p.skip_m ? fuse_stride : 0;
-    if (units) { p.unit_launch = DPH_UNIT_LAUNCHES - 1; dph_launch_scan_units(p, false, 1, 0xFFFFu, tau, st); }
-    else dph_launch_scan(p, false, full_tiles, 1, tau, nset, st);
-    if (h->sc.profile && !retry) { (void)hipEventRecord(ev.second, st); h->sc.prof_events.v.push_back(ev); }
+    if (!retry) h->sc.stats.fused_stride = p.skip_m ? b.fuse_stride : 0;
+    bracketed(h, h->sc.profile && !retry, h->sc.prof_events, st, [&] {
+        if (units) { p.unit_launch = DPH_UNIT_LAUNCHES - 1; dph_launch_scan_units(p, false, 1, 0xFFFFu, b.tau, st); }
+        else dph_launch_scan(p, false, full_tiles, 1, b.tau, st);
+    });
     dph_launch_refine(p, st);
-    dph_select_args a{};
-    a.lut = h->sh->lut_dev; a.k = k; a.C = C; a.rmax = h->sh->rmax; a.rmax_all = h->sh->rmax_all; a.delta_max = h->sh->delta_max;
-    a.offset = h->sh->offset; a.scale = h->sh->scale; a.tau = tau; a.rowmap = rowmap;
-    a.D = D; a.I = I; a.status = status; a.bound_out = bound_out; a.ik_out = ik_out; a.fail_out = fail_out;
-    dph_launch_select(p, a, st);
+    dph_select_args s{};
+    s.lut = h->sh->lut_dev; s.k = a.k; s.C = a.C(); s.rmax = h->sh->rmax; s.rmax_all = h->sh->rmax_all; s.delta_max = h->sh->delta_max;
+    s.offset = h->sh->offset; s.scale = h->sh->scale; s.tau = b.tau; s.rowmap = a.rowmap;
+    s.D = a.D; s.I = a.I; s.status = a.status; s.bound_out = a.bound_out; s.ik_out = a.ik_out; s.fail_out = a.fail_out;
+    dph_launch_select(p, s, st);
     // A row whose certificate did not close although every pair is in its bucket (near-ties at the k-th place: a run of near-duplicate
     // rows) does not need another scan of the shard -- the wider re-score of the retry pass can run on the bucket it already has.
     // Second look, same buckets, C = DPH_SELECT_C_MAX, flagged rows only (the others leave at once: ~5 us when nothing failed); only
     // rows that lost pairs or still fail go on to the re-scan.  (Document-ordered dump, batch 64: one such row in every fourth batch
     // used to cost a whole extra 18.5 ms scan of the 170 M-row shard.)
-    if (!retry && a.fail_out && C < DPH_SELECT_C_MAX) {
-        dph_select_args w = a;
+    if (!retry && s.fail_out && s.C < DPH_SELECT_C_MAX) {
+        dph_select_args w = s;
         w.C = DPH_SELECT_C_MAX;
-        w.only_failed = a.fail_out;
-        w.reselect_count = h->sc.counters + 3;
+        w.only_failed = s.fail_out;
+        w.reselect_count = &h->sc.counters.p->reselect;
         dph_launch_select(p, w, st);
     }
     if (!retry) h->sc.stats.scan_launches++;
@@ -1268,18 +1252,19 @@ static int check_search_args(dph_index* h, const void* x, int64_t n, int k, int 
     return DPH_OK;
 }
 
-// The fp64 full scan of the (up to DPH_EXACT_ROWS_DEV) rows in exact_rows / exact_x, their count in counters[1]: the probe masks of those
+// The fp64 full scan of the (up to DPH_EXACT_ROWS_DEV) rows in exact_rows / exact_x, their count in counters.fail_retry: the probe masks of those
 // rows on an IVF search, then the exact scan with `rounds` tightening rounds.
 static void launch_exact_fallback(dph_index* h, int k, int nprobe, float* D, int64_t* I, int32_t* status, int rounds, hipStream_t st) {
     const unsigned* mask = nullptr;
+    const int* n_rows = &h->sc.counters.p->fail_retry;
     if (h->sh->row_ids && nprobe > 0) {
         dph_coarse_args c = coarse_args(*h->sh, h->sc.exact_x, 0, DPH_EXACT_ROWS_DEV, nprobe, h->sc.ivf.coarse_scores);
-        c.gate = h->sc.counters + 1;
+        c.gate = n_rows;
         c.listmask = h->sc.ivf.listmask; c.mask_words = 8; c.tilemask = h->sc.ivf.tilemask;
         dph_launch_coarse(c, h->sc.coarse, st);
         mask = h->sc.ivf.tilemask;
     }
-    dph_launch_exact(h->sh->db, h->sh->n_rows, make_idmap(h->sh), h->sc.exact_x, h->sh->lut_dev, h->sc.exact_rows, h->sc.counters + 1, DPH_EXACT_ROWS_DEV,
+    dph_launch_exact(h->sh->db, h->sh->n_rows, make_idmap(h->sh), h->sc.exact_x, h->sh->lut_dev, h->sc.exact_rows, n_rows, DPH_EXACT_ROWS_DEV,
                      k, h->sh->row_ids, mask, D, I, status, h->sc.exact_scratch, h->sc.exact_scratch.n, st, rounds);
 }
 
@@ -1290,90 +1275,126 @@ static void launch_exact_fallback(dph_index* h, int k, int nprobe, float* D, int
 //      DPH_SELECT_C_MAX re-scored candidates;
 //   3. up to DPH_EXACT_ROWS_DEV rows that still fail go through the fp64 full scan.
 // Afterwards status[r] = 0 for every row except the ones neither step could settle (counted by dph_search_get_stats).
-static int search_core(dph_index* h, const float* x_dev, int64_t n, int k, int nprobe, float* D_dev, int64_t* I_dev,
-                       int32_t* status_dev, hipStream_t st, const search_opts& opt) {
-    if (opt.phase != 2) {
+static int search_core(dph_index* h, const float* x_dev, int64_t n, const pass_args& call, hipStream_t st, search_stage stage = SEARCH_WHOLE) {
+    dph_search_counters* const cnt = h->sc.counters;
+    if (stage != SEARCH_FINISH) {
         quantize(h, h->sc.q_main, x_dev, n, nullptr, st, true);
-        HIPCHK(hipMemsetAsync(h->sc.counters + 3, 0, 2 * sizeof(int), st));   // rows the in-pass wide re-select certifies (run_pass); non-finite rows
+        // rows the in-pass wide re-select certifies (pass_scan_select); non-finite rows
+        HIPCHK(hipMemsetAsync(&cnt->reselect, 0, offsetof(dph_search_counters, nonfinite) + sizeof(int) - offsetof(dph_search_counters, reselect), st));
     }
-    // from here on the rows are read from the quantiser's clean copy (phase 2: the one the prepare stage left), never from the caller's buffer
+    // from here on the rows are read from the quantiser's clean copy (finish: the one the prepare stage left), never from the caller's buffer
     x_dev = h->sc.q_main.x;
-    const bool sample_only = opt.top_out != nullptr;
     for (int64_t q0 = 0; q0 < n;) {
         const int64_t left = n - q0;
-        const bool units = use_units(h, nprobe);                    // a unit pass serves up to DPH_PASS_MAX rows
+        const bool units = use_units(h, call.nprobe);               // a unit pass serves up to DPH_PASS_MAX rows
         const int qb = units ? 1 : ((left > DPH_QROWS && h->tune.max_qb >= 2) ? 2 : 1);
         const int nq = (int)std::min<int64_t>(left, units ? (int64_t)DPH_PASS_MAX : (int64_t)DPH_QROWS * qb);
         dph_pass p = make_pass(h, h->sc.q_main, x_dev, (int)q0, nq, qb);
-        int rc = run_pass(h, p, k, nprobe, opt.tau_ext ? opt.tau_ext + q0 : nullptr,
-                          sample_only ? opt.top_out + q0 * DPH_SAMPLE_KEEP : nullptr, nullptr, D_dev, I_dev, status_dev,
-                          opt.bound_out, h->sc.ik_dev, h->sc.fail_dev, st, opt.phase);
+        pass_args a = call;
+        if (a.tau_ext) a.tau_ext += q0;
+        if (a.top_out) a.top_out += q0 * DPH_SAMPLE_KEEP;
+        a.ik_out = h->sc.ik_dev; a.fail_out = h->sc.fail_dev;
+        int rc;
+        if (stage == SEARCH_FINISH) {
+            // (flat shards: no probe set-up) the prepare stage's last bound; its finest level's candidates wait in the buckets
+            rc = pass_scan_select(h, p, a, h->sc.prep.bound, st);
+        } else {
+            rc = pass_probe(h, p, a, st);
+            pass_bound b{a.tau_ext, 0};                              // the bounded form brings its bounds and skips the ladder
+            if (!rc && !a.tau_ext) {
+                // (prepare: the sampled levels run on the few CUs of a side stream -- as many workgroups as those, not one per CU of the chip)
+                dph_pass lp = p;
+                if (stage == SEARCH_PREPARE && h->tune.side_grid > 0) lp.grid = std::min(h->tune.side_grid, h->tune.grid);
+                rc = pass_ladder(h, lp, a, st, &b);
+            }
+            if (rc) return rc;
+            if (stage == SEARCH_PREPARE) h->sc.prep.bound = b;
+            else if (!a.top_out) rc = pass_scan_select(h, p, a, b, st);   // (the sample form stops after the ladder)
+        }
         if (rc) return rc;
         q0 += nq;
     }
-    if (sample_only || opt.phase == 1) { HIPCHK(hipGetLastError()); return DPH_OK; }
+    if (call.top_out || stage == SEARCH_PREPARE) { HIPCHK(hipGetLastError()); return DPH_OK; }
     if (!h->tune.retry_chain) {
         // measurements / diagnostics: no re-scan, no fp64 fallback -- the counters say how many rows the first attempt left open, their
         // status stays 1 (and the buckets of the last pass stay readable: dph_debug_bucket_counts)
-        dph_launch_compact_failing(h->sc.fail_dev, n, 0, nullptr, h->sc.retry_rows, h->sc.counters + 0, nullptr, 0, st);
-        HIPCHK(hipMemcpyAsync(h->sc.counters + 1, h->sc.counters + 0, sizeof(int), hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(h->sc.counters + 2, h->sc.counters + 0, sizeof(int), hipMemcpyDeviceToDevice, st));
-        dph_launch_nonfinite_fix(h->sc.q_main.nf, n, k, D_dev, I_dev, status_dev, opt.bound_out, h->sc.counters + 4, st);
+        dph_launch_compact_failing(h->sc.fail_dev, n, 0, nullptr, h->sc.retry_rows, &cnt->fail_first, nullptr, 0, st);
+        HIPCHK(hipMemcpyAsync(&cnt->fail_retry, &cnt->fail_first, sizeof(int), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(&cnt->unsettled, &cnt->fail_first, sizeof(int), hipMemcpyDeviceToDevice, st));
+        dph_launch_nonfinite_fix(h->sc.q_main.nf, n, call.k, call.D, call.I, call.status, call.bound_out, &cnt->nonfinite, st);
         HIPCHK(hipGetLastError());
         return DPH_OK;
     }
 
     // ---- 2. on-device retry of the rows that failed
-    dph_launch_compact_failing(h->sc.fail_dev, n, 0, x_dev, h->sc.retry_rows, h->sc.counters + 0, h->sc.q_retry.x, (int)n, st);
-    quantize(h, h->sc.q_retry, h->sc.q_retry.x, n, h->sc.counters + 0, st);
-    dph_launch_retry_tau(h->sc.counters + 0, n, h->sc.retry_rows, h->sc.ik_dev, h->sc.q_retry.qinfo, h->sh->rmax, h->sh->delta_max, h->sh->scale,
+    dph_launch_compact_failing(h->sc.fail_dev, n, 0, x_dev, h->sc.retry_rows, &cnt->fail_first, h->sc.q_retry.x, (int)n, st);
+    quantize(h, h->sc.q_retry, h->sc.q_retry.x, n, &cnt->fail_first, st);
+    dph_launch_retry_tau(&cnt->fail_first, n, h->sc.retry_rows, h->sc.ik_dev, h->sc.q_retry.qinfo, h->sh->rmax, h->sh->delta_max, h->sh->scale,
                          h->sc.retry_tau, st);
     HIPCHK(hipMemsetAsync(h->sc.fail2_dev, 0, (size_t)n * 4, st));
     for (int64_t q0 = 0; q0 < n; q0 += DPH_QROWS) {
         const int nq = (int)std::min<int64_t>(n - q0, DPH_QROWS);
         dph_pass p = make_pass(h, h->sc.q_retry, h->sc.q_retry.x, (int)q0, nq, 1);
-        p.gate = h->sc.counters + 0;
+        p.gate = &cnt->fail_first;
         p.gate_base = (int)q0;
         p.wave_counts = h->sc.wave_counts + (size_t)h->tune.grid * 8;
-        int rc = run_pass(h, p, k, nprobe, h->sc.retry_tau + q0, nullptr, h->sc.retry_rows, D_dev, I_dev, status_dev, opt.bound_out,
-                          nullptr, h->sc.fail2_dev, st);
+        pass_args a = call;                                          // (never the sample form: that returned above)
+        a.tau_ext = h->sc.retry_tau + q0; a.rowmap = h->sc.retry_rows; a.fail_out = h->sc.fail2_dev;
+        int rc = pass_probe(h, p, a, st);
+        if (!rc) rc = pass_scan_select(h, p, a, pass_bound{a.tau_ext, 0}, st);
         if (rc) return rc;
     }
     // ---- 3. fp64 full scan for (up to DPH_EXACT_ROWS_DEV of) the rows the retry could not settle
-    dph_launch_compact_failing(h->sc.fail2_dev, n, 0, x_dev, h->sc.exact_rows, h->sc.counters + 1, h->sc.exact_x, DPH_EXACT_ROWS_DEV, st);
-    launch_exact_fallback(h, k, nprobe, D_dev, I_dev, status_dev, 1, st);
+    dph_launch_compact_failing(h->sc.fail2_dev, n, 0, x_dev, h->sc.exact_rows, &cnt->fail_retry, h->sc.exact_x, DPH_EXACT_ROWS_DEV, st);
+    launch_exact_fallback(h, call.k, call.nprobe, call.D, call.I, call.status, 1, st);
     // the result of a non-finite query row: ids -1, scores -FLT_MAX, status DPH_ROW_NONFINITE (its stand-in was searched like any row)
-    dph_launch_nonfinite_fix(h->sc.q_main.nf, n, k, D_dev, I_dev, status_dev, opt.bound_out, h->sc.counters + 4, st);
+    dph_launch_nonfinite_fix(h->sc.q_main.nf, n, call.k, call.D, call.I, call.status, call.bound_out, &cnt->nonfinite, st);
     // rows still flagged 1 (more than DPH_EXACT_ROWS_DEV failures, or boundary ties beyond the fp64 scan's buffer)
-    dph_launch_compact_failing(status_dev, n, 1, nullptr, h->sc.retry_rows, h->sc.counters + 2, nullptr, 0, st);
+    dph_launch_compact_failing(call.status, n, 1, nullptr, h->sc.retry_rows, &cnt->unsettled, nullptr, 0, st);
     HIPCHK(hipGetLastError());
     return DPH_OK;
 }
 
-static int read_counters(dph_index* h, hipStream_t st, int out[5]) {
-    HIPCHK(hipMemcpyAsync(out, h->sc.counters, 5 * sizeof(int), hipMemcpyDeviceToHost, st));
+static int read_counters(dph_index* h, hipStream_t st, dph_search_counters* out) {
+    HIPCHK(hipMemcpyAsync(out, h->sc.counters, sizeof(*out), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return DPH_OK;
 }
 
+// The one rule from the counters of a call to its statistics (s.rows set by the entry point); `unsettled`: rows still open at the end.
+// (A non-finite row's stand-in is searched and certified like any row; the row is counted once, as non-finite.)
+static void fill_stats(dph_search_stats& s, const dph_search_counters& c, int unsettled) {
+    s.nonfinite = c.nonfinite;
+    s.certified_fast = s.rows - c.fail_first - c.reselect - c.nonfinite;
+    s.certified_wide = c.fail_first - c.fail_retry + c.reselect;
+    s.certified_reselect = c.reselect;        // the first look could not certify, the wider look at the same bucket could (no re-scan)
+    s.exact_fallback = c.fail_retry - unsettled;
+    s.uncertified = unsettled;
+}
+
+// a call starts its statistics; pending = its device counters are read back only when dph_search_get_stats asks
+static void begin_stats(dph_index* h, int64_t n, bool pending) {
+    h->sc.stats = dph_search_stats{};
+    h->sc.stats.rows = (int32_t)n;
+    h->sc.stats_pending = pending;
+}
 static int pq_nprobe(const dph_index* h, int nprobe) { return nprobe > 0 ? nprobe : (h->tune.default_nprobe > 0 ? h->tune.default_nprobe : 256); }
 
 static int search_dev_impl(dph_index* h, const float* x_dev, int64_t n, int k, int nprobe, float* D_dev, int64_t* I_dev,
-                           int32_t* status_dev, void* stream, const char* who, const search_opts& opt = search_opts()) {
+                           int32_t* status_dev, void* stream, const char* who, pass_args opt = pass_args()) {
     if (h && h->sh->pq) {
         if (!x_dev || !D_dev || !I_dev || !status_dev || n < 0 || k <= 0 || k > 1024) return fail(DPH_E_ARG, std::string(who) + ": bad arguments");
         if (opt.top_out || opt.tau_ext) return fail(DPH_E_STATE, std::string(who) + ": the sharded two-phase entry points do not serve PQ indexes");
         if (!h->sh->finalized) return fail(DPH_E_STATE, std::string(who) + ": call dph_index_finalize first");
         if (n == 0) return DPH_OK;
         HIPCHK(hipSetDevice(h->device));
-        if (!h->sc.counters) HIPCHK(h->sc.counters.alloc(8));
-        h->sc.stats = dph_search_stats{};
-        h->sc.stats.rows = (int32_t)n;
-        h->sc.stats_pending = false;
+        if (!h->sc.counters) HIPCHK(h->sc.counters.alloc(1));
+        begin_stats(h, n, false);
         const int rc = dph_pq_search_dev(h->sh->pq, x_dev, n, k, pq_nprobe(h, nprobe), D_dev, I_dev, status_dev, (hipStream_t)stream);
         if (rc) return fail(rc, std::string(who) + ": " + dph_last_error());
-        // the rows' statuses, counted on the device: [0] uncertified, [1] non-finite (read back when dph_search_get_stats asks)
-        dph_launch_count_status(status_dev, n, h->sc.counters, (hipStream_t)stream);
+        // the rows' statuses, counted on the device: uncertified, non-finite (read back when dph_search_get_stats asks)
+        static_assert(offsetof(dph_search_counters, pq.nonfinite) == offsetof(dph_search_counters, pq.uncertified) + sizeof(int), "out[0], out[1]");
+        dph_launch_count_status(status_dev, n, &h->sc.counters.p->pq.uncertified, (hipStream_t)stream);
         HIPCHK(hipGetLastError());
         h->sc.stats_pending = true;
         return DPH_OK;
@@ -1385,10 +1406,9 @@ static int search_dev_impl(dph_index* h, const float* x_dev, int64_t n, int k, i
     HIPCHK(hipSetDevice(h->device));
     rc = ensure_scratch(h, n, 0);
     if (rc) return rc;
-    h->sc.stats = dph_search_stats{};
-    h->sc.stats.rows = (int32_t)n;
-    h->sc.stats_pending = true;
-    return search_core(h, x_dev, n, k, nprobe, D_dev, I_dev, status_dev, (hipStream_t)stream, opt);
+    begin_stats(h, n, true);
+    opt.k = k; opt.nprobe = nprobe; opt.D = D_dev; opt.I = I_dev; opt.status = status_dev;
+    return search_core(h, x_dev, n, opt, (hipStream_t)stream);
 }
 
 static int search_host_impl(dph_index* h, const float* x, int64_t n, int k, int nprobe, float* D, int64_t* I, const char* who) {
@@ -1425,21 +1445,16 @@ static int search_host_impl(dph_index* h, const float* x, int64_t n, int k, int 
     rc = ensure_scratch(h, n, k);
     if (rc) return rc;
     hipStream_t st = nullptr;
-    h->sc.stats = dph_search_stats{};
-    h->sc.stats.rows = (int32_t)n;
-    h->sc.stats_pending = false;
+    begin_stats(h, n, false);
     HIPCHK(hipMemcpyAsync(h->sc.q_main.x, x, (size_t)n * DPH_DIM * 4, hipMemcpyHostToDevice, st));
-    rc = search_core(h, h->sc.q_main.x, n, k, nprobe, h->sc.D_dev, h->sc.I_dev, h->sc.status_dev, st, search_opts());
+    pass_args call;
+    call.k = k; call.nprobe = nprobe; call.D = h->sc.D_dev; call.I = h->sc.I_dev; call.status = h->sc.status_dev;
+    rc = search_core(h, h->sc.q_main.x, n, call, st);
     if (rc) return rc;
-    int c[5] = {0, 0, 0, 0, 0};
-    rc = read_counters(h, st, c);
+    dph_search_counters c{};
+    rc = read_counters(h, st, &c);
     if (rc) return rc;
-    h->sc.stats.nonfinite = c[4];
-    // (a non-finite row's stand-in is searched and certified like any row; the row is counted once, as non-finite)
-    h->sc.stats.certified_fast = (int32_t)(n - c[0] - c[3] - c[4]);
-    h->sc.stats.certified_wide = c[0] - c[1] + c[3];
-    h->sc.stats.certified_reselect = c[3];
-    int left = c[2];
+    int left = c.unsettled;
     if (left > 0) {
         // more failures than the on-device fallback serves per call: feed it the rest, DPH_EXACT_ROWS_DEV at a time
         std::vector<int32_t> status((size_t)n);
@@ -1451,8 +1466,8 @@ static int search_host_impl(dph_index* h, const float* x, int64_t n, int k, int 
         for (size_t i0 = 0; i0 < rest.size(); i0 += DPH_EXACT_ROWS_DEV) {
             const int m = (int)std::min<size_t>(DPH_EXACT_ROWS_DEV, rest.size() - i0);
             HIPCHK(hipMemcpyAsync(h->sc.exact_rows, rest.data() + i0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(h->sc.counters + 1, &m, sizeof(int), hipMemcpyHostToDevice, st));
-            dph_launch_gather_rows(h->sc.q_main.x, h->sc.exact_rows, h->sc.counters + 1, h->sc.exact_x, DPH_EXACT_ROWS_DEV, st);
+            HIPCHK(hipMemcpyAsync(&h->sc.counters.p->fail_retry, &m, sizeof(int), hipMemcpyHostToDevice, st));
+            dph_launch_gather_rows(h->sc.q_main.x, h->sc.exact_rows, &h->sc.counters.p->fail_retry, h->sc.exact_x, DPH_EXACT_ROWS_DEV, st);
             launch_exact_fallback(h, k, nprobe, h->sc.D_dev, h->sc.I_dev, h->sc.status_dev, 3, st);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));
@@ -1461,8 +1476,7 @@ static int search_host_impl(dph_index* h, const float* x, int64_t n, int k, int 
         left = 0;
         for (int64_t r = 0; r < n; ++r) left += status[r] == 1;
     }
-    h->sc.stats.uncertified = left;
-    h->sc.stats.exact_fallback = c[1] - left;
+    fill_stats(h->sc.stats, c, left);
     HIPCHK(hipMemcpy(D, h->sc.D_dev, (size_t)n * k * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(I, h->sc.I_dev, (size_t)n * k * 8, hipMemcpyDeviceToHost));
     if (left > 0) return fail(DPH_E_UNCERTIFIED, std::string(who) + ": boundary ties exceed the exact-scan buffer");
@@ -1496,9 +1510,9 @@ int dph_search_sample_dev(dph_index* h, const float* x_dev, int64_t n, int32_t* 
     HIPCHK(hipSetDevice(h->device));
     int rc = ensure_scratch(h, n, 0);
     if (rc) return rc;
-    search_opts opt;
-    opt.top_out = top_dev;
-    return search_core(h, x_dev, n, 1, default_nprobe(h), nullptr, nullptr, nullptr, (hipStream_t)stream, opt);
+    pass_args call;
+    call.nprobe = default_nprobe(h); call.top_out = top_dev;
+    return search_core(h, x_dev, n, call, (hipStream_t)stream);
 }
 
 int dph_union_bounds_dev(int device, const int32_t* top_parts, int n_parts, int64_t n, int32_t* tau_dev, void* stream) {
@@ -1512,7 +1526,7 @@ int dph_union_bounds_dev(int device, const int32_t* top_parts, int n_parts, int6
 int dph_search_bounded_dev(dph_index* h, const float* x_dev, int64_t n, int k, const int32_t* tau_dev, float* D_dev,
                            int64_t* I_dev, int32_t* status_dev, double* bound_dev, void* stream) {
     if (!tau_dev || !bound_dev) return fail(DPH_E_ARG, "dph_search_bounded_dev: null buffer");
-    search_opts opt;
+    pass_args opt;
     opt.tau_ext = tau_dev;
     opt.bound_out = bound_dev;
     return search_dev_impl(h, x_dev, n, k, default_nprobe(h), D_dev, I_dev, status_dev, stream, "dph_search_bounded_dev", opt);
@@ -1537,9 +1551,9 @@ int dph_search_prepare_dev(dph_index* h, const float* x_dev, int64_t n, int k, v
     rc = ensure_scratch(h, n, 0);
     if (rc) return rc;
     h->sc.prep = dph_scratch::prepared();
-    search_opts opt;
-    opt.phase = 1;
-    rc = search_core(h, x_dev, n, k, 0, nullptr, nullptr, nullptr, (hipStream_t)stream, opt);
+    pass_args call;
+    call.k = k;
+    rc = search_core(h, x_dev, n, call, (hipStream_t)stream, SEARCH_PREPARE);
     if (rc) return rc;
     h->sc.prep.valid = true; h->sc.prep.n = n; h->sc.prep.k = k;
     return DPH_OK;
@@ -1553,12 +1567,10 @@ int dph_search_finish_dev(dph_index* h, const float* x_dev, int64_t n, int k, fl
         return fail(DPH_E_STATE, "dph_search_finish_dev: no matching dph_search_prepare_dev on this handle (same n, same k)");
     HIPCHK(hipSetDevice(h->device));
     h->sc.prep.valid = false;
-    h->sc.stats = dph_search_stats{};
-    h->sc.stats.rows = (int32_t)n;
-    h->sc.stats_pending = true;
-    search_opts opt;
-    opt.phase = 2;
-    return search_core(h, x_dev, n, k, 0, D_dev, I_dev, status_dev, (hipStream_t)stream, opt);
+    begin_stats(h, n, true);
+    pass_args call;
+    call.k = k; call.D = D_dev; call.I = I_dev; call.status = status_dev;
+    return search_core(h, x_dev, n, call, (hipStream_t)stream, SEARCH_FINISH);
 }
 
 // A stream whose kernels run on the CUs [first_cu, first_cu + n_cus) of the device's CU-mask bit order only (MI355X: bit i is a CU of
@@ -1587,25 +1599,17 @@ int dph_search_get_stats(dph_index* h, dph_search_stats* out) {
     if (h->sc.stats_pending) {
         // device-pointer call: the counters live on the device until somebody asks (this synchronises the device)
         HIPCHK(hipSetDevice(h->device));
-        int c[5] = {0, 0, 0, 0, 0};
+        dph_search_counters c{};
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(c, h->sc.counters, sizeof(c), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&c, h->sc.counters, sizeof(c), hipMemcpyDeviceToHost));
         h->sc.stats_pending = false;
         if (h->sh->pq) {                     // (search_dev_impl: the statuses the PQ search wrote, counted)
-            h->sc.stats.uncertified = c[0];
-            h->sc.stats.nonfinite = c[1];
-            h->sc.stats.certified_fast = h->sc.stats.rows - c[0] - c[1];
-            *out = h->sc.stats;
-            return DPH_OK;
+            h->sc.stats.uncertified = c.pq.uncertified;
+            h->sc.stats.nonfinite = c.pq.nonfinite;
+            h->sc.stats.certified_fast = h->sc.stats.rows - c.pq.uncertified - c.pq.nonfinite;
+        } else {
+            fill_stats(h->sc.stats, c, c.unsettled);
         }
-        h->sc.stats.nonfinite = c[4];
-        // c[3]: rows the first look could not certify and the wider look at the same bucket could (no re-scan)
-        h->sc.stats.certified_fast = h->sc.stats.rows - c[0] - c[3] - c[4];      // (non-finite rows are counted once, as non-finite)
-        h->sc.stats.certified_wide = c[0] - c[1] + c[3];
-        h->sc.stats.certified_reselect = c[3];
-        h->sc.stats.exact_fallback = c[1] - c[2];
-        h->sc.stats.uncertified = c[2];
-        h->sc.stats_pending = false;
     }
     *out = h->sc.stats;
     return DPH_OK;
@@ -1851,7 +1855,8 @@ int dph_profile_enable(dph_index* h, int on) {
     return DPH_OK;
 }
 
-static int drain_events(dph_index* h, dph_event_pairs& evs, double* total_out, int* cnt_out) {
+// every bracketed launch of `evs` since the last read: total and count, each duration to each_out[0 .. cap) when asked; the pairs go back to prof_free
+static int drain_events(dph_index* h, dph_event_pairs& evs, double* total_out, int* cnt_out, double* each_out = nullptr, int cap = 0) {
     double total = 0.0;
     int cnt = 0;
     for (auto& ev : evs.v) {
@@ -1859,6 +1864,7 @@ static int drain_events(dph_index* h, dph_event_pairs& evs, double* total_out, i
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
         total += ms;
+        if (cnt < cap) each_out[cnt] = ms;
         ++cnt;
         h->sc.prof_free.v.push_back(ev);
     }
@@ -1882,19 +1888,7 @@ int dph_profile_read_each(dph_index* h, int which, double* ms_out, int cap, int*
     if (!h || !n_out || cap < 0 || (cap > 0 && !ms_out)) return fail(DPH_E_ARG, "dph_profile_read_each: bad arguments");
     if (h->sh->pq) return dph_pq_profile_read_each(h->sh->pq, ms_out, cap, n_out);
     HIPCHK(hipSetDevice(h->device));
-    auto& evs = which ? h->sc.prof_events_ladder : h->sc.prof_events;
-    int n = 0;
-    for (auto& ev : evs.v) {
-        HIPCHK(hipEventSynchronize(ev.second));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
-        if (n < cap) ms_out[n] = ms;
-        ++n;
-        h->sc.prof_free.v.push_back(ev);
-    }
-    evs.v.clear();
-    *n_out = n;
-    return DPH_OK;
+    return drain_events(h, which ? h->sc.prof_events_ladder : h->sc.prof_events, nullptr, n_out, ms_out, cap);
 }
 
 int dph_profile_read_all(dph_index* h, double* scan_ms_total, int* scan_launches, double* ladder_ms_total, int* ladder_launches) {
@@ -1905,36 +1899,43 @@ int dph_profile_read_all(dph_index* h, double* scan_ms_total, int* scan_launches
     return drain_events(h, h->sc.prof_events, scan_ms_total, scan_launches);
 }
 
+// what the two scan hooks below share: the query rows copied and quantised, one pass over them (a list-major shard: every tile)
+static int debug_scan_pass(dph_index* h, const float* x, int64_t n, hipStream_t st, dph_pass* p) {
+    HIPCHK(hipSetDevice(h->device));
+    int rc = ensure_scratch(h, n, 0);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h->sc.q_main.x, x, (size_t)n * DPH_DIM * 4, hipMemcpyHostToDevice, st));
+    quantize(h, h->sc.q_main, h->sc.q_main.x, n, nullptr, st);
+    *p = make_pass(h, h->sc.q_main, h->sc.q_main.x, 0, (int)n, n > DPH_QROWS ? 2 : 1);
+    if (h->sh->row_ids) p->tilemask = h->sh->onesmask;
+    return DPH_OK;
+}
+
 int dph_debug_scan_buckets(dph_index* h, const float* x, int64_t n, const int32_t* tau_host, int tile_stride,
                            uint64_t* keys_host, uint32_t* counts_host) {
     if (!h || !x || !keys_host || !counts_host || n <= 0 || n > DPH_QROWS * DPH_MAX_QB || tile_stride < 1)
         return fail(DPH_E_ARG, "dph_debug_scan_buckets: bad arguments");
     if (!h->sh->finalized) return fail(DPH_E_STATE, "dph_debug_scan_buckets: call dph_index_finalize first");
-    HIPCHK(hipSetDevice(h->device));
-    int rc = ensure_scratch(h, n, 0);
-    if (rc) return rc;
     hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(h->sc.q_main.x, x, (size_t)n * DPH_DIM * 4, hipMemcpyHostToDevice, st));
-    quantize(h, h->sc.q_main, h->sc.q_main.x, n, nullptr, st);
-    const int qb = n > DPH_QROWS ? 2 : 1;
-    dph_pass p = make_pass(h, h->sc.q_main, h->sc.q_main.x, 0, (int)n, qb);
-    if (h->sh->row_ids) p.tilemask = h->sh->onesmask;
+    dph_pass p;
+    int rc = debug_scan_pass(h, x, n, st, &p);
+    if (rc) return rc;
     const int* tau = nullptr;
     if (tau_host) {
         HIPCHK(hipMemcpyAsync(h->sc.tau_dev, tau_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
         tau = h->sc.tau_dev;
     }
     const int64_t tiles = (h->sh->n_tiles + tile_stride - 1) / tile_stride;
-    dph_launch_scan(p, tile_stride > 1, tiles, tile_stride, tau, 4, st);
+    dph_launch_scan(p, tile_stride > 1, tiles, tile_stride, tau, st);
     dph_launch_refine(p, st);
     HIPCHK(hipGetLastError());
-    std::vector<unsigned> cnt((size_t)2 * DPH_PASS_MAX);
-    HIPCHK(hipMemcpyAsync(cnt.data(), h->sc.bucket_counts, cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    std::vector<dph_pass_counters> cnt(1);
+    HIPCHK(hipMemcpyAsync(cnt.data(), p.cnt, sizeof(dph_pass_counters), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (int64_t q = 0; q < n; ++q) {
         // bit 31 of the count reports lost pairs (the pair pool ran dry) for that row
-        const unsigned c = cnt[(size_t)q] < (unsigned)DPH_BUCKET_CAP ? cnt[(size_t)q] : (unsigned)DPH_BUCKET_CAP;
-        counts_host[q] = c | (cnt[(size_t)(DPH_PASS_MAX + q)] ? 0x80000000u : 0u);
+        const unsigned c = std::min(cnt[0].bucket_counts[q], (unsigned)DPH_BUCKET_CAP);
+        counts_host[q] = c | (cnt[0].overflow[q] ? 0x80000000u : 0u);
         HIPCHK(hipMemcpy(keys_host + q * DPH_BUCKET_CAP, h->sc.buckets + q * DPH_BUCKET_CAP, (size_t)c * 8, hipMemcpyDeviceToHost));
     }
     return DPH_OK;
@@ -1945,15 +1946,10 @@ int dph_debug_scan_time(dph_index* h, const float* x, int64_t n, int iters, floa
         return fail(DPH_E_ARG, "dph_debug_scan_time: bad arguments");
     if (!h->sh->finalized) return fail(DPH_E_STATE, "dph_debug_scan_time: call dph_index_finalize first");
     if (h->sh->pq) return fail(DPH_E_STATE, "dph_debug_scan_time: a PQ index has no filter scan");
-    HIPCHK(hipSetDevice(h->device));
-    int rc = ensure_scratch(h, n, 0);
-    if (rc) return rc;
     hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(h->sc.q_main.x, x, (size_t)n * DPH_DIM * 4, hipMemcpyHostToDevice, st));
-    quantize(h, h->sc.q_main, h->sc.q_main.x, n, nullptr, st);
-    const int qb = n > DPH_QROWS ? 2 : 1;
-    dph_pass p = make_pass(h, h->sc.q_main, h->sc.q_main.x, 0, (int)n, qb);
-    if (h->sh->row_ids) p.tilemask = h->sh->onesmask;
+    dph_pass p;
+    int rc = debug_scan_pass(h, x, n, st, &p);
+    if (rc) return rc;
     // a bound no high-digit score reaches (|H| <= 127 * 128 * 768 < 2^24 = (2^31 - 1 - lmax) >> 7 for any lmax < 2^24): the
     // launch streams and multiplies everything and emits nothing
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->sc.tau_dev, 0x7fffffff, (size_t)n, st));
@@ -1962,7 +1958,7 @@ int dph_debug_scan_time(dph_index* h, const float* x, int64_t n, int iters, floa
     HIPCHK(hipEventCreate(&b));
     for (int i = 0; i < iters; ++i) {
         HIPCHK(hipEventRecord(a, st));
-        dph_launch_scan(p, false, h->sh->n_tiles, 1, h->sc.tau_dev, 4, st);
+        dph_launch_scan(p, false, h->sh->n_tiles, 1, h->sc.tau_dev, st);
         HIPCHK(hipEventRecord(b, st));
         HIPCHK(hipEventSynchronize(b));
         HIPCHK(hipEventElapsedTime(&ms_out[i], a, b));
@@ -1975,11 +1971,11 @@ int dph_debug_scan_time(dph_index* h, const float* x, int64_t n, int iters, floa
 
 int dph_debug_bucket_counts(dph_index* h, int64_t n, uint32_t* raw_out, uint32_t* overflow_out) {
     if (!h || !raw_out || !overflow_out || n <= 0 || n > DPH_PASS_MAX) return fail(DPH_E_ARG, "dph_debug_bucket_counts: bad arguments");
-    if (!h->sc.bucket_counts) return fail(DPH_E_STATE, "dph_debug_bucket_counts: no search yet");
+    if (!h->sc.pass_cnt) return fail(DPH_E_STATE, "dph_debug_bucket_counts: no search yet");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(raw_out, h->sc.bucket_counts, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(overflow_out, h->sc.bucket_counts + DPH_PASS_MAX, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(raw_out, h->sc.pass_cnt.p->bucket_counts, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(overflow_out, h->sc.pass_cnt.p->overflow, (size_t)n * 4, hipMemcpyDeviceToHost));
     return DPH_OK;
 }
 
@@ -2060,11 +2056,11 @@ int64_t dph_debug_guided_segment(int64_t u, int64_t n_tiles, int grid, int seg_m
 
 int dph_debug_units(dph_index* h, int32_t out[4]) {
     if (!h || !out) return fail(DPH_E_ARG, "dph_debug_units: null");
-    if (!h->sc.ivf.unit_counts) return fail(DPH_E_STATE, "dph_debug_units: no unit scan on this shard");
+    if (!h->sc.ivf.unit_cnt) return fail(DPH_E_STATE, "dph_debug_units: no unit scan on this shard");
     HIPCHK(hipSetDevice(h->device));
-    int c[4 + DPH_UNIT_LAUNCHES];
-    HIPCHK(hipMemcpy(c, h->sc.ivf.unit_counts, sizeof(c), hipMemcpyDeviceToHost));
-    out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[4 + DPH_UNIT_LAUNCHES - 1];
+    dph_unit_counters c;
+    HIPCHK(hipMemcpy(&c, h->sc.ivf.unit_cnt, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = c.chunks; out[1] = c.units; out[2] = c.error; out[3] = c.next[DPH_UNIT_LAUNCHES - 1];
     return DPH_OK;
 }
 

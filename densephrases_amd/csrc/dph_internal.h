@@ -1,7 +1,9 @@
 // dph_internal.h -- shared constants / device structs of libdph (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <atomic>
 #include <string>
 #include <utility>
@@ -54,6 +56,21 @@ struct dph_event_pairs {
         return ev;
     }
 };
+
+// Dynamic LDS beyond the default limit is granted per kernel and device: asked for once (`done`: a static of the call site -- zero-
+// initialised; handles are searched from several threads), asked again by the next call when it was refused.
+static inline void dph_allow_lds(const void* kernel, const char* name, size_t bytes, int dev, std::atomic<bool> (&done)[64]) {
+    if (dev >= 0 && dev < 64 && done[dev]) return;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(%s, %zu B of LDS): %s\n", name, bytes, hipGetErrorString(e));
+    if (dev >= 0 && dev < 64) done[dev] = e == hipSuccess;
+}
+static inline int dph_current_device() { int dev = 0; (void)hipGetDevice(&dev); return dev; }
+#define DPH_ALLOW_LDS(KERNEL, BYTES, DEV)                                           \
+    do {                                                                            \
+        static std::atomic<bool> done_[64];                                         \
+        dph_allow_lds((const void*)KERNEL, #KERNEL, (BYTES), (DEV), done_);         \
+    } while (0)
 
 // ---------------------------------------------------------------- geometry of the scan
 // A scan workgroup is 4 waves, one per SIMD, one workgroup per CU.  Wave w owns QB groups of 32 query rows for the
@@ -110,6 +127,27 @@ struct dph_aux_layout {
 #define DPH_UNIT_TILES 256          // tiles per segment (6 MiB of the dump; 1024 measured no better: the tail grows)
 #define DPH_UNIT_SLOTS 128
 #define DPH_UNIT_LAUNCHES 8         // work-queue counters per pass (one per scan launch: ladder levels + the full scan)
+
+// The small device counters of a pass, each ONE allocation of one struct (dph_api.hip): host code hands the kernels field addresses.
+// Cleared in front of every scan launch (dph_clear_pass_counters): the scan counts and flags, the outlier / refine kernels behind it
+// fill the buckets, threshold / select read all of it.
+struct dph_pass_counters {
+    int queue_head;                             // work-queue head of the flat / masked scan
+    unsigned chunks_claimed;                    // chunks claimed from the pair pool: the scan kernels find it one word behind queue_head
+    unsigned pad[2];
+    unsigned bucket_counts[DPH_PASS_MAX];       // keys in every query row's bucket
+    unsigned overflow[DPH_PASS_MAX];            // row lost pairs (the pair pool ran dry)
+};
+static_assert(offsetof(dph_pass_counters, chunks_claimed) == offsetof(dph_pass_counters, queue_head) + sizeof(int) &&
+              offsetof(dph_pass_counters, bucket_counts) == 16 && sizeof(dph_pass_counters) == 16 + 2 * DPH_PASS_MAX * sizeof(unsigned),
+              "dph_scan_kernel derives chunks_claimed from queue_head; the accumulating scan clears the 16 bytes in front of the bucket counts");
+// ... and of a unit-scan pass: cleared and written by dph_launch_units_build, the heads popped by the scan launches
+struct dph_unit_counters {
+    int chunks, units, error, spare;            // chunks and units of the pass (dph_units_offsets_kernel); error: a table would have overflowed
+    int next[DPH_UNIT_LAUNCHES];                // work-queue heads, one per scan launch
+};
+static_assert(offsetof(dph_unit_counters, units) == 4 && offsetof(dph_unit_counters, error) == 8 && offsetof(dph_unit_counters, next) == 16,
+              "dph_units_offsets_kernel / dph_units_build_kernel write counts[0..2]");
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -190,7 +228,7 @@ __host__ __device__ static inline int64_t dph_guided_segment(int64_t u, int64_t 
 // everything a pass of the search pipeline shares (filled by dph_api.hip, consumed by the launchers)
 struct dph_pass {
     // shard
-    const int8_t* db; int64_t n_rows; int64_t n_tiles; int64_t id_base; const int64_t* row_ids; dph_idmap idmap;
+    const int8_t* db; int64_t n_rows; const int64_t* row_ids; dph_idmap idmap;
     int grid;                           // scan workgroups (= CUs)
     // the pass
     int qb;                             // 1 or 2: 128*qb query rows
@@ -206,8 +244,7 @@ struct dph_pass {
     // IVF unit scan (unit_recs != NULL): work queue + gathered query fragments, see DPH_PASS_MAX above
     const int4* unit_recs;              // {first tile of the list, first tile of the segment, end tile, chunk}
     const int4* unit_list_recs;         // the same per chunk for the whole list (what the ladder levels walk)
-    const int* unit_counts;             // [0] chunks, [1] units (device side, written by dph_units_build_kernel)
-    int* unit_next;                     // [DPH_UNIT_LAUNCHES] work-queue heads
+    dph_unit_counters* unit_cnt;        // chunks, units (device side, written by dph_launch_units_build) and the work-queue heads
     int unit_launch;                    // which head the next scan launch uses
     const int* slot_q;                  // [chunk][128] query row of the pass in that MFMA column, -1 = empty
     const int8_t* unit_frags;           // [chunk][4][DPH_QGROUP_FRAG_BYTES] high digits in fragment order
@@ -219,10 +256,8 @@ struct dph_pass {
     // scratch
     uint2* pairs; unsigned* chunk_fill;         // [DPH_POOL_CHUNKS][DPH_CHUNK_PAIRS] pair pool, pairs in every claimed chunk
     unsigned* wave_counts;                      // [grid*4][2] (pairs, emit-path triggers) of every scan wave: statistics
-    uint64_t* buckets; unsigned* bucket_counts; // [DPH_PASS_MAX][DPH_BUCKET_CAP], [DPH_PASS_MAX]
-    unsigned* overflow;                         // [DPH_PASS_MAX] row lost pairs (the pair pool ran dry)
-    int* queue_head;                            // [0] work-queue head of the flat / masked scan, [1] chunks claimed from the
-                                                // pair pool; zeroed (with the bucket counts and overflow flags) by every scan launch
+    uint64_t* buckets;                          // [DPH_PASS_MAX][DPH_BUCKET_CAP]
+    dph_pass_counters* cnt;                     // queue head, claimed chunks, bucket counts, overflow flags: zeroed by every scan launch
     int seg_tiles;                              // shortest queue segment in tiles (full scans; sampled levels: fewer)
     int sched;                                  // hand-over schedule of the flat full scan (dph_scan.hip hand_pos): 0 lock step, 1 wave after wave, 2 interleaved
     // the full scan behind a FUSED finest ladder level of stride S: skip_m = ceil(2^29 / (S - 1)) makes the scan skip the tiles
@@ -246,8 +281,7 @@ void dph_launch_aux_build(const int8_t* db, int64_t n_rows, int64_t n_rows_padde
                           const dph_aux_layout& lay, int norm_unit, int8_t* aux, hipStream_t st);
 // filter scan of every `tile_stride`-th tile (n_tiles_visit of them) under the per-row bounds tau (NULL = none: every
 // row of the visited tiles is emitted -- cold start of the ladder / tiny shards)
-void dph_launch_scan(const dph_pass& p, bool sample, int64_t n_tiles_visit, int tile_stride, const int* tau, int nset,
-                     hipStream_t st);
+void dph_launch_scan(const dph_pass& p, bool sample, int64_t n_tiles_visit, int tile_stride, const int* tau, hipStream_t st);
 // unit scan: every unit visits the tiles of its segment whose index inside the list is a multiple of `tile_stride`;
 // `rowmask` (bit r = accumulator register r of a lane, 2 rows each) restricts what a visited tile may emit (cold level)
 void dph_launch_scan_units(const dph_pass& p, bool sample, int tile_stride, unsigned rowmask, const int* tau, hipStream_t st);
@@ -350,10 +384,24 @@ long long dph_coarse_filter_debug_pool(const dph_coarse_scratch& s, unsigned* lk
 void dph_launch_bf16_hi(const float* v, int64_t n_rows, int tiled, unsigned short* hi, hipStream_t st);
 int64_t dph_bf16_hi_rows(int64_t n_rows, int tiled);
 void dph_launch_bf16_split(const float* v, int64_t n_elems, unsigned* packed, hipStream_t st);
-// work queue of a unit-scan pass from the probe masks: chunks, slot tables, unit records, gathered fragments
-void dph_launch_units_build(const unsigned* listmask, int nlist, const int* list_tile0, const int8_t* q1, int q0,
-                            int chunk_cap, int unit_cap, int* unit_counts, int* slot_q, int4* unit_recs, int4* unit_list_recs,
-                            int8_t* unit_frags, int2* unit_offsets, int spread, hipStream_t st, bool x16);
+// IVF scratch of a handle: what a pass writes (dph_index_set_ivf sizes it from the lists) ...
+struct dph_ivf_pass {
+    dev_buf<float> coarse_scores;       // [coarse_rows, nlist] fp32: query x centroid scores of the current pass
+    int coarse_rows = 0;
+    dev_buf<unsigned> listmask;         // [nlist][8]   bit j of word w: query row 32w+j of the pass probes the list
+    dev_buf<unsigned> tilemask;         // [n_tiles][8] the same per tile (what the scan reads)
+    dev_buf<int2> unit_offsets;         // [nlist] first chunk / first unit of every list in the current pass
+    dev_buf<unsigned> listmask_u;       // [nlist][DPH_UNIT_WORDS]
+    dev_buf<dph_unit_counters> unit_cnt;    // [1]
+};
+// ... and the work queue of a unit-scan pass of up to DPH_PASS_MAX query rows (sized from nprobe)
+struct dph_unit_queue {
+    dev_buf<int> slot_q; dev_buf<int4> unit_recs, unit_list_recs; dev_buf<int8_t> unit_frags;
+    int chunk_cap = 0, unit_cap = 0;
+};
+// work queue of a unit-scan pass from the probe masks ivf.listmask_u: chunks, slot tables, unit records, gathered fragments
+void dph_launch_units_build(const dph_ivf_pass& ivf, const dph_unit_queue& uq, int nlist, const int* list_tile0, const int8_t* q1, int q0,
+                            int spread, bool x16, hipStream_t st);
 // list assignment (arg-max over the centroids, fused: no score matrix); rows = fp32 [n,768] or int8 rows + the shard's LUT
 void dph_launch_assign(const void* rows, bool rows_int8, const float* lut, int64_t n, const float* centroids, int nlist,
                        const float* bias, int32_t* best, float* gap, hipStream_t st);

@@ -1177,22 +1177,9 @@ __global__ __launch_bounds__(256) void dph_tilemask_kernel(const int32_t* __rest
     }
 }
 
-// Dynamic LDS beyond the default limit is granted per kernel and device: asked for once (`done`: a static of the call site -- zero-
-// initialised; handles are searched from several threads), asked again by the next call when it was refused.
-static void cg_allow_lds(const void* kernel, const char* name, size_t bytes, int dev, std::atomic<bool> (&done)[64]) {
-    if (dev >= 0 && dev < 64 && done[dev]) return;
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(%s, %zu B of LDS): %s\n", name, bytes, hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) done[dev] = e == hipSuccess;
-}
-#define CG_ALLOW_LDS(KERNEL, BYTES, DEV)                                            \
-    do {                                                                            \
-        static std::atomic<bool> done_[64];                                         \
-        cg_allow_lds((const void*)KERNEL, #KERNEL, (BYTES), (DEV), done_);          \
-    } while (0)
 #define CS_LDS ((size_t)2 * CS_CAND * 4)        // dynamic LDS of the select kernel (static + dynamic exceed 64 KiB)
 
-static void cs_select_allow_lds(int dev) { CG_ALLOW_LDS(dph_coarse_select_kernel, CS_LDS, dev); }
+static void cs_select_allow_lds(int dev) { DPH_ALLOW_LDS(dph_coarse_select_kernel, CS_LDS, dev); }
 
 // the parts of the scratch (dph_internal.h): all of a part or nothing; a failed hipMalloc is not the caller's error
 static bool ensure_chain(dph_coarse_scratch::chain_part& c) {
@@ -1219,13 +1206,12 @@ static bool ensure_filter(dph_coarse_scratch::filter_part& f) {
 // the chain: score GEMM (f32, or bf16x3 from CG_BF16X3_MIN lists on), probe selection, tile masks
 void dph_launch_coarse(const dph_coarse_args& a, dph_coarse_scratch& s, hipStream_t st) {
     if (a.clear_mask && a.listmask) (void)hipMemsetAsync(a.listmask, 0, (size_t)a.nlist * a.mask_words * 4, st);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
+    const int dev = dph_current_device();
     const bool bf16x3 = a.nlist >= CG_BF16X3_MIN;
     const dim3 gg((a.nlist + CG_LISTS - 1) / CG_LISTS, (a.n_q + CG_QROWS - 1) / CG_QROWS);
     if (bf16x3 && a.c_pk && a.x_pk) {
         const size_t lds3 = (size_t)4 * CG_LISTS * CG3P_LD * 2;
-        CG_ALLOW_LDS(dph_coarse_gemm_bf16x3_pipe_kernel, lds3, dev);
+        DPH_ALLOW_LDS(dph_coarse_gemm_bf16x3_pipe_kernel, lds3, dev);
         hipLaunchKernelGGL(dph_coarse_gemm_bf16x3_pipe_kernel, gg, dim3(256), lds3, st, a.q0, a.n_q, a.gate, a.gate_base, a.nlist, a.scores, a.c_pk, a.x_pk);
     }
     else if (bf16x3)
@@ -1278,10 +1264,10 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
     if (cus <= 0 || cus > 256) cus = 256;           // (the wave statistics hold 256 CUs)
     const size_t lds128 = (size_t)2 * CG_LISTS * (CF_K + 8) * 2;
     const size_t lds_v3 = (size_t)2 * CG_QROWS * (CF_K + 8) * 2 + (size_t)CF_HIT_CAP * 10;
-    CG_ALLOW_LDS(dph_coarse_filter_gemm_kernel<true>, lds128, dev);
-    CG_ALLOW_LDS(dph_coarse_filter_gemm_kernel<false>, lds128, dev);
-    CG_ALLOW_LDS((dph_coarse_filter_gemm_kernel<false, true>), lds128, dev);
-    CG_ALLOW_LDS(dph_coarse_filter_gemm2_kernel, lds_v3, dev);
+    DPH_ALLOW_LDS(dph_coarse_filter_gemm_kernel<true>, lds128, dev);
+    DPH_ALLOW_LDS(dph_coarse_filter_gemm_kernel<false>, lds128, dev);
+    DPH_ALLOW_LDS((dph_coarse_filter_gemm_kernel<false, true>), lds128, dev);
+    DPH_ALLOW_LDS(dph_coarse_filter_gemm2_kernel, lds_v3, dev);
     cs_select_allow_lds(dev);
     const int qt = (n_q + CG_QROWS - 1) / CG_QROWS;
     const int np = a.nprobe < nlist ? a.nprobe : nlist;
@@ -1509,16 +1495,15 @@ __global__ __launch_bounds__(256) void dph_units_gather_kernel(const int* __rest
     }
 }
 
-void dph_launch_units_build(const unsigned* listmask, int nlist, const int* list_tile0, const int8_t* q1, int q0,
-                            int chunk_cap, int unit_cap, int* unit_counts, int* slot_q, int4* unit_recs, int4* unit_list_recs,
-                            int8_t* unit_frags, int2* unit_offsets, int spread, hipStream_t st, bool x16) {
-    // unit_counts[4] and the DPH_UNIT_LAUNCHES work-queue heads behind it are one allocation
-    (void)hipMemsetAsync(unit_counts, 0, (size_t)(4 + DPH_UNIT_LAUNCHES) * sizeof(int), st);
-    hipLaunchKernelGGL(dph_units_offsets_kernel, dim3(1), dim3(UO_THREADS), 0, st, listmask, nlist, list_tile0, unit_offsets,
-                       unit_counts);
-    hipLaunchKernelGGL(dph_units_build_kernel, dim3((nlist + 3) / 4), dim3(256), 0, st, listmask, nlist, list_tile0, chunk_cap,
-                       unit_cap, unit_offsets, unit_counts, slot_q, unit_recs, unit_list_recs, spread);
-    hipLaunchKernelGGL(dph_units_gather_kernel, dim3(chunk_cap, 4), dim3(256), 0, st, unit_counts, slot_q, q1, q0, unit_frags, x16);
+void dph_launch_units_build(const dph_ivf_pass& ivf, const dph_unit_queue& uq, int nlist, const int* list_tile0, const int8_t* q1, int q0,
+                            int spread, bool x16, hipStream_t st) {
+    int* const counts = &ivf.unit_cnt.p->chunks;          // the kernels' view: [0] chunks, [1] units, [2] error (dph_unit_counters)
+    (void)hipMemsetAsync(ivf.unit_cnt.p, 0, sizeof(dph_unit_counters), st);
+    hipLaunchKernelGGL(dph_units_offsets_kernel, dim3(1), dim3(UO_THREADS), 0, st, ivf.listmask_u.p, nlist, list_tile0, ivf.unit_offsets.p,
+                       counts);
+    hipLaunchKernelGGL(dph_units_build_kernel, dim3((nlist + 3) / 4), dim3(256), 0, st, ivf.listmask_u.p, nlist, list_tile0, uq.chunk_cap,
+                       uq.unit_cap, ivf.unit_offsets.p, counts, uq.slot_q.p, uq.unit_recs.p, uq.unit_list_recs.p, spread);
+    hipLaunchKernelGGL(dph_units_gather_kernel, dim3(uq.chunk_cap, 4), dim3(256), 0, st, counts, uq.slot_q.p, q1, q0, uq.unit_frags.p, x16);
 }
 
 // ---- list assignment of database rows for the list builder (replaces the add-to-index step of

@@ -165,14 +165,14 @@ void dph_launch_refine(const dph_pass& p, hipStream_t st) {
     if (n_out > 0 && !p.accumulate) {
         if (p.unit_recs)
             hipLaunchKernelGGL(dph_outlier_kernel, dim3((n_out + 15) / 16, 32), dim3(256), 0, st, p.db, outliers, n_out, p.q1, p.q2,
-                               p.q0, p.gate, p.gate_base, p.n_q, p.listmask, p.tile_list, p.mask_words, p.buckets, p.bucket_counts, p.qaux, p.aux_lay);
+                               p.q0, p.gate, p.gate_base, p.n_q, p.listmask, p.tile_list, p.mask_words, p.buckets, p.cnt->bucket_counts, p.qaux, p.aux_lay);
         else
             hipLaunchKernelGGL(dph_outlier_kernel, dim3((n_out + 15) / 16, 32), dim3(256), 0, st, p.db, outliers, n_out, p.q1, p.q2,
-                               p.q0, p.gate, p.gate_base, p.n_q, p.tilemask, (const int32_t*)nullptr, 8, p.buckets, p.bucket_counts, p.qaux, p.aux_lay);
+                               p.q0, p.gate, p.gate_base, p.n_q, p.tilemask, (const int32_t*)nullptr, 8, p.buckets, p.cnt->bucket_counts, p.qaux, p.aux_lay);
     }
     hipLaunchKernelGGL(dph_refine_kernel, dim3(REFINE_GRID), dim3(256), 0, st, p.db, p.row_ids, p.pairs,
-                       (const unsigned*)p.queue_head + 1, p.chunk_fill, p.q1, p.q2, p.q0, p.gate, p.gate_base, p.n_q, outliers, n_out,
-                       p.buckets, p.bucket_counts, p.qaux, p.aux_lay);
+                       &p.cnt->chunks_claimed, p.chunk_fill, p.q1, p.q2, p.q0, p.gate, p.gate_base, p.n_q, outliers, n_out,
+                       p.buckets, p.cnt->bucket_counts, p.qaux, p.aux_lay);
 }
 
 // ------------------------------------------------------------------------------------------ sampled bound
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(THR_THREADS) void dph_threshold_kernel(
 }
 
 void dph_launch_threshold(const dph_pass& p, int kp, const int* floor_tau, int* tau_out, int* top_out, hipStream_t st) {
-    hipLaunchKernelGGL(dph_threshold_kernel, dim3(p.unit_recs ? p.n_q : DPH_QROWS * p.qb), dim3(THR_THREADS), 0, st, p.buckets, p.bucket_counts,
+    hipLaunchKernelGGL(dph_threshold_kernel, dim3(p.unit_recs ? p.n_q : DPH_QROWS * p.qb), dim3(THR_THREADS), 0, st, p.buckets, p.cnt->bucket_counts,
                        top_out ? DPH_SAMPLE_KEEP : kp, p.gate, p.gate_base, p.n_q, floor_tau, tau_out, top_out, p.outliers, p.n_out);
 }
 

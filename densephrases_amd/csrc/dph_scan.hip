@@ -998,14 +998,7 @@ __global__ __launch_bounds__(DPH_SCAN_THREADS, 1) void dph_coarse_scan_teams_ker
 void dph_launch_coarse_scan_teams(const void* img, int64_t n_lists, const void* qfrag, int n_q, int n_groups, const unsigned* est_keys, uint2* pairs,
                                   unsigned* chunk_fill, unsigned* wave_counts, int* counters, int grid, hipStream_t st) {
     const size_t lds = DPH_SCAN_LDS_BYTES;
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)dph_coarse_scan_teams_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(dph_coarse_scan_teams_kernel, %zu B of LDS): %s\n", lds, hipGetErrorString(e));
-        if (dev >= 0 && dev < 64) attr_set[dev] = e == hipSuccess;
-    }
+    DPH_ALLOW_LDS(dph_coarse_scan_teams_kernel, lds, dph_current_device());
     const int64_t n_tiles = (n_lists + DPH_TILE_ROWS - 1) / DPH_TILE_ROWS;
     const int n_teams = grid / n_groups;
     const int seg = (int)std::max<int64_t>(1, (n_tiles + n_teams - 1) / n_teams);
@@ -1018,14 +1011,7 @@ void dph_launch_coarse_scan_teams(const void* img, int64_t n_lists, const void* 
 void dph_launch_coarse_scan(const void* img, int64_t n_lists, const void* qfrag, int n_q, const unsigned* est_keys, uint2* pairs,
                             unsigned* chunk_fill, unsigned* wave_counts, int* counters, int grid, hipStream_t st) {
     const size_t lds = DPH_SCAN_LDS_BYTES;
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)dph_coarse_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(dph_coarse_scan_kernel, %zu B of LDS): %s\n", lds, hipGetErrorString(e));
-        if (dev >= 0 && dev < 64) attr_set[dev] = e == hipSuccess;
-    }
+    DPH_ALLOW_LDS(dph_coarse_scan_kernel, lds, dph_current_device());
     const int64_t n_tiles = (n_lists + DPH_TILE_ROWS - 1) / DPH_TILE_ROWS;
     // ONE segment per workgroup (a quarter millisecond of streaming: every further pop is a pipeline refill of ~3 us, and a queue's
     // last segment an imbalance of its own length); long quantizers only, so the segments are thousands of rows
@@ -1036,13 +1022,11 @@ void dph_launch_coarse_scan(const void* img, int64_t n_lists, const void* qfrag,
                        (unsigned*)counters + 2);
 }
 
-// [4] work-queue head, chunks claimed from the pair pool (+ padding) | [DPH_PASS_MAX] bucket counts | [DPH_PASS_MAX]
-// overflow flags: one allocation (dph_api.hip), cleared by one memset in front of every scan launch -- the scan counts
-// and flags, the outlier / refine kernels behind it fill the buckets, threshold / select read all of it.
+// dph_pass_counters (dph_internal.h), cleared by one memset in front of every scan launch
 void dph_clear_pass_counters(const dph_pass& p, hipStream_t st) {
     // an ACCUMULATING scan (the full scan behind a fused ladder level) keeps the buckets and flags of that level: only the
     // work-queue head and the pair pool start over
-    (void)hipMemsetAsync(p.queue_head, 0, p.accumulate ? (size_t)4 * 4 : (size_t)(4 + 2 * DPH_PASS_MAX) * 4, st);
+    (void)hipMemsetAsync(p.cnt, 0, p.accumulate ? offsetof(dph_pass_counters, bucket_counts) : sizeof(dph_pass_counters), st);
 }
 
 int dph_scan_grid(int device) {
@@ -1054,15 +1038,7 @@ int dph_scan_grid(int device) {
 template <int QB, int NSET, bool IVF, int ROLE, int SCHED = 0, bool AUX = false>
 static void launch_scan_t(const dph_pass& p, int64_t n_tiles_visit, int tile_stride, const int* tau, hipStream_t st) {
     const size_t lds = DPH_SCAN_LDS_BYTES;
-    static std::atomic<bool> attr_set[64];       // the attribute is per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)dph_scan_kernel<QB, NSET, IVF, ROLE, SCHED, AUX>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(dph_scan_kernel, %zu B of LDS): %s\n", lds, hipGetErrorString(e));
-        if (dev >= 0 && dev < 64) attr_set[dev] = e == hipSuccess;
-    }
+    DPH_ALLOW_LDS((dph_scan_kernel<QB, NSET, IVF, ROLE, SCHED, AUX>), lds, dph_current_device());
     const int8_t* qf = p.qfrag_hi + (int64_t)(p.q0 / DPH_QGROUP) * DPH_QGROUP_FRAG_BYTES;
     dph_clear_pass_counters(p, st);
     // shortest segment the queue deals: p.seg_tiles at the end of a full scan, down to one tile on the sampled levels (the
@@ -1071,8 +1047,8 @@ static void launch_scan_t(const dph_pass& p, int64_t n_tiles_visit, int tile_str
     const int seg = (int)std::max<int64_t>(1, std::min<int64_t>(p.seg_tiles, fair));
     hipLaunchKernelGGL((dph_scan_kernel<QB, NSET, IVF, ROLE, SCHED, AUX>), dim3(p.grid), dim3(DPH_SCAN_THREADS), lds, st, p.db,
                        p.n_rows, n_tiles_visit, tile_stride, qf, p.n_q, p.gate, p.gate_base, tau,
-                       p.lmax ? p.lmax + p.q0 : nullptr, p.tilemask, p.pairs, p.wave_counts, p.queue_head, seg, p.row_ids,
-                       p.chunk_fill, p.overflow, p.skip_m, p.aux, p.aux_lay.stride,
+                       p.lmax ? p.lmax + p.q0 : nullptr, p.tilemask, p.pairs, p.wave_counts, &p.cnt->queue_head, seg, p.row_ids,
+                       p.chunk_fill, p.cnt->overflow, p.skip_m, p.aux, p.aux_lay.stride,
                        p.qaux ? p.qaux + (int64_t)p.q0 * DPH_AUX_SLOTS : nullptr);
 }
 
@@ -1100,9 +1076,7 @@ static void launch_scan_a(const dph_pass& p, bool sample, int64_t n_tiles_visit,
     }
 #undef DPH_GO
 }
-void dph_launch_scan(const dph_pass& p, bool sample, int64_t n_tiles_visit, int tile_stride, const int* tau, int nset,
-                     hipStream_t st) {
-    (void)nset;
+void dph_launch_scan(const dph_pass& p, bool sample, int64_t n_tiles_visit, int tile_stride, const int* tau, hipStream_t st) {
     if (p.unit_recs) { dph_launch_scan_units(p, sample, tile_stride, 0xFFFFu, tau, st); return; }
     // a shard with aux rows (dph_index_finalize: rogue dimensions or heavy-tailed row norms) runs the instantiations with the aux k-step
     if (p.aux) launch_scan_a<true>(p, sample, n_tiles_visit, tile_stride, tau, st);
@@ -1112,30 +1086,24 @@ void dph_launch_scan(const dph_pass& p, bool sample, int64_t n_tiles_visit, int 
 template <bool AUX>
 static void launch_scan_units_a(const dph_pass& p, bool sample, int tile_stride, unsigned rowmask, const int* tau, hipStream_t st) {
     const size_t lds = DPH_SCAN_LDS_BYTES;
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)dph_scan_units_kernel<0, AUX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dph_scan_units_kernel<1, AUX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(dph_scan_units_kernel, %zu B of LDS): %s\n", lds, hipGetErrorString(e));
-        if (dev >= 0 && dev < 64) attr_set[dev] = e == hipSuccess;
-    }
-    int* next = p.unit_next + p.unit_launch;
+    const int dev = dph_current_device();
+    DPH_ALLOW_LDS((dph_scan_units_kernel<0, AUX>), lds, dev);
+    DPH_ALLOW_LDS((dph_scan_units_kernel<1, AUX>), lds, dev);
+    int* next = p.unit_cnt->next + p.unit_launch;
     const int* lmax = p.lmax ? p.lmax + p.q0 : nullptr;
     const int8_t* qaux = p.qaux ? p.qaux + (int64_t)p.q0 * DPH_AUX_SLOTS : nullptr;
     dph_clear_pass_counters(p, st);
-    unsigned* const pool_head = (unsigned*)p.queue_head + 1;
+    unsigned* const pool_head = &p.cnt->chunks_claimed;
     // a ladder level walks the table of WHOLE lists (one unit per chunk: a few strided tiles each -- cutting those into
     // segments would only multiply the per-unit start-up), the full scan the table of segments
     if (sample)
         hipLaunchKernelGGL((dph_scan_units_kernel<1, AUX>), dim3(p.grid), dim3(DPH_SCAN_THREADS), lds, st, p.db, p.n_rows, tile_stride,
-                           rowmask, p.unit_frags, p.n_q, tau, lmax, p.unit_list_recs, p.unit_counts + 0, next, p.slot_q, p.pairs,
-                           p.wave_counts, p.row_ids, pool_head, p.chunk_fill, p.overflow, p.aux, p.aux_lay.stride, qaux);
+                           rowmask, p.unit_frags, p.n_q, tau, lmax, p.unit_list_recs, &p.unit_cnt->chunks, next, p.slot_q, p.pairs,
+                           p.wave_counts, p.row_ids, pool_head, p.chunk_fill, p.cnt->overflow, p.aux, p.aux_lay.stride, qaux);
     else
         hipLaunchKernelGGL((dph_scan_units_kernel<0, AUX>), dim3(p.grid), dim3(DPH_SCAN_THREADS), lds, st, p.db, p.n_rows, tile_stride,
-                           rowmask, p.unit_frags, p.n_q, tau, lmax, p.unit_recs, p.unit_counts + 1, next, p.slot_q, p.pairs,
-                           p.wave_counts, p.row_ids, pool_head, p.chunk_fill, p.overflow, p.aux, p.aux_lay.stride, qaux);
+                           rowmask, p.unit_frags, p.n_q, tau, lmax, p.unit_recs, &p.unit_cnt->units, next, p.slot_q, p.pairs,
+                           p.wave_counts, p.row_ids, pool_head, p.chunk_fill, p.cnt->overflow, p.aux, p.aux_lay.stride, qaux);
 }
 void dph_launch_scan_units(const dph_pass& p, bool sample, int tile_stride, unsigned rowmask, const int* tau, hipStream_t st) {
     if (p.aux) launch_scan_units_a<true>(p, sample, tile_stride, rowmask, tau, st);

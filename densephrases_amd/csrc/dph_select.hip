@@ -242,17 +242,10 @@ __global__ __launch_bounds__(SEL_THREADS) void dph_select_kernel(
 
 void dph_launch_select(const dph_pass& p, const dph_select_args& a, hipStream_t st) {
     const size_t lds = (size_t)DPH_POOL_MAX * 8 + (DPH_DIM + 256) * 4 + (size_t)a.C * 16 + 64 + 16;
-    static std::atomic<bool> attr_set[64];       // the attribute is per device; sized for the largest C (retry passes)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)dph_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)((size_t)DPH_POOL_MAX * 8 + (DPH_DIM + 256) * 4 + (size_t)DPH_SELECT_C_MAX * 16 + 80));
-        if (e != hipSuccess) fprintf(stderr, "libdph: hipFuncSetAttribute(dph_select_kernel): %s\n", hipGetErrorString(e));
-        if (dev >= 0 && dev < 64) attr_set[dev] = e == hipSuccess;
-    }
-    hipLaunchKernelGGL(dph_select_kernel, dim3(p.unit_recs ? p.n_q : DPH_QROWS * p.qb), dim3(SEL_THREADS), lds, st, p.buckets, p.bucket_counts,
-                       p.overflow, p.db, p.idmap, p.x, p.qinfo, a.lut, p.row_ids, p.outliers, p.n_out, a.rmax_all, p.q0,
+    // (once per device: sized for the largest C, the retry passes')
+    DPH_ALLOW_LDS(dph_select_kernel, (size_t)DPH_POOL_MAX * 8 + (DPH_DIM + 256) * 4 + (size_t)DPH_SELECT_C_MAX * 16 + 80, dph_current_device());
+    hipLaunchKernelGGL(dph_select_kernel, dim3(p.unit_recs ? p.n_q : DPH_QROWS * p.qb), dim3(SEL_THREADS), lds, st, p.buckets, p.cnt->bucket_counts,
+                       p.cnt->overflow, p.db, p.idmap, p.x, p.qinfo, a.lut, p.row_ids, p.outliers, p.n_out, a.rmax_all, p.q0,
                        p.gate, p.gate_base, p.n_q, a.k, a.C, a.rmax, a.delta_max, a.offset, a.scale, a.tau, a.rowmap, a.D, a.I,
                        a.status, a.bound_out, a.ik_out, a.fail_out, a.only_failed, a.reselect_count);
 }
