@@ -193,6 +193,7 @@ int dph_index_assign_dev(dph_index* h, int64_t row0, int64_t n, const float* cen
  * FAISS runs k-means with the quantizer -- an IndexFlatIP -- as the assignment index and normalises the centroids of
  * inner-product indexes: ClusteringParameters::spherical).  All pointers are device pointers.
  *   dph_index_gather_rows_dev: sample_dev[i] = int8 row rows_idx_dev[i] (stored-row index) of the resident shard, [m,768].
+ *                              An index below 0 or >= the stored rows yields an all-zero row (nothing is read for it).
  *   dph_kmeans_step_dev:       ONE Lloyd iteration over int8 rows [m,768] in the shard's codec: assignment = arg-max_l
  *                              <x_r, c_l> + bias[l] (the fused MFMA GEMM + arg-max of dph_ivf_assign_dev; bias NULL = the
  *                              inner-product assignment FAISS uses for these indexes), update = de-quantised mean of the

@@ -146,8 +146,9 @@ def test_ivf_recall_and_window_on_list_major_shard():
 @pytest.mark.parametrize("units", [0, 1])
 def test_ivf_coarse_quantizer_with_many_lists(units):
     """nlist = 20000 (beyond what the round-1 LDS-resident coarse kernel could hold): scores from the MFMA GEMM, radix
-    select of the nprobe-th, float64 re-rank of the band -- the probed sets, hence the results, equal the float64
-    oracle's."""
+    select of the nprobe-th, float64 re-rank of the band -- the results equal the float64 oracle's over ITS probed
+    sets.  (Equal results do not show equal probed sets: a list swapped at the nprobe-th place rarely holds a top-10 row.
+    tests/test_coarse_probe_sets.py holds the probed sets themselves against the float64 order.)"""
     rng = np.random.default_rng(31)
     n_rows, nlist, nprobe, n_q, k = 40000, 20000, 300, 40, 10
     xb, centres = _clustered_db(rng, n_rows, 24)
