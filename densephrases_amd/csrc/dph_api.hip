@@ -134,10 +134,9 @@ struct dph_scratch {
     dph_search_stats stats{};
     bool stats_pending = false;          // device counters of the last device-pointer call not read back yet
     // measurement hook: event pairs around scan launches
-    bool profile = false;
+    dph_profiler prof;
     dph_event_pairs prof_events;         // around the full-scan launches
     dph_event_pairs prof_events_ladder;  // around the scan launches of the ladder levels
-    dph_event_pairs prof_free;
     // the two-stage form of a search (dph_search_prepare_dev / dph_search_finish_dev): what the prepare stage left behind
     struct prepared { bool valid = false; int64_t n = 0; int k = 0; pass_bound bound; } prep;
 };
@@ -171,14 +170,6 @@ static void build_lut(dph_shard* s) {
 // the rows, metadata and shard constants of an index that has twins (or is one) are shared and stay as they are
 #define DPH_NOT_TWINNED(h, who) \
     do { if ((h) && ((h)->twin_of || (h)->n_twins > 0)) return fail(DPH_E_STATE, std::string(who) + ": not on an index that has twins or is one"); } while (0)
-
-// the profile bracket of a scan launch: a (start, stop) event pair around it, kept in `list` until dph_profile_read* drains it
-template <typename Launch> static void bracketed(dph_index* h, bool on, dph_event_pairs& list, hipStream_t st, Launch launch) {
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (on) { ev = h->sc.prof_free.take(); (void)hipEventRecord(ev.first, st); }
-    launch();
-    if (on) { (void)hipEventRecord(ev.second, st); list.v.push_back(ev); }
-}
 
 extern "C" {
 
@@ -1185,7 +1176,7 @@ static int pass_ladder(dph_index* h, dph_pass p, const pass_args& a, hipStream_t
     for (size_t i = 0; i < levels.size(); ++i) {
         const int stride = levels[i].stride;
         const int* tau = b->tau;
-        bracketed(h, h->sc.profile && !a.retry(), h->sc.prof_events_ladder, st, [&] {
+        h->sc.prof.bracket(h->sc.prof.on && !a.retry() ? &h->sc.prof_events_ladder : nullptr, st, [&] {
             if (units) { p.unit_launch = (int)i; dph_launch_scan_units(p, true, stride, levels[i].rowmask, tau, st); }
             else dph_launch_scan(p, true, (h->sh->n_tiles + stride - 1) / stride, stride, tau, st);
         });
@@ -1216,7 +1207,7 @@ static int pass_scan_select(dph_index* h, dph_pass p, const pass_args& a, const 
         if (visit > 0) { p.skip_m = m; p.accumulate = true; full_tiles = visit; }
     }
     if (!retry) h->sc.stats.fused_stride = p.skip_m ? b.fuse_stride : 0;
-    bracketed(h, h->sc.profile && !retry, h->sc.prof_events, st, [&] {
+    h->sc.prof.bracket(h->sc.prof.on && !retry ? &h->sc.prof_events : nullptr, st, [&] {
         if (units) { p.unit_launch = DPH_UNIT_LAUNCHES - 1; dph_launch_scan_units(p, false, 1, 0xFFFFu, b.tau, st); }
         else dph_launch_scan(p, false, full_tiles, 1, b.tau, st);
     });
@@ -1840,37 +1831,9 @@ int dph_merge_records_dev(int device, const float* D_parts, const int64_t* I_par
 int dph_profile_enable(dph_index* h, int on) {
     if (!h) return fail(DPH_E_ARG, "null");
     if (h->sh->pq) return dph_pq_profile(h->sh->pq, on);
-    h->sc.profile = on != 0;
-    if (h->sc.profile && h->sc.prof_free.v.size() < 256) {
-        // create the events now: the first hipEventCreate of a process can take ~100 ms, and it must not land in a
-        // timed region
-        HIPCHK(hipSetDevice(h->device));
-        while (h->sc.prof_free.v.size() < 256) {
-            std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-            HIPCHK(hipEventCreate(&ev.first));
-            HIPCHK(hipEventCreate(&ev.second));
-            h->sc.prof_free.v.push_back(ev);
-        }
-    }
-    return DPH_OK;
-}
-
-// every bracketed launch of `evs` since the last read: total and count, each duration to each_out[0 .. cap) when asked; the pairs go back to prof_free
-static int drain_events(dph_index* h, dph_event_pairs& evs, double* total_out, int* cnt_out, double* each_out = nullptr, int cap = 0) {
-    double total = 0.0;
-    int cnt = 0;
-    for (auto& ev : evs.v) {
-        HIPCHK(hipEventSynchronize(ev.second));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
-        total += ms;
-        if (cnt < cap) each_out[cnt] = ms;
-        ++cnt;
-        h->sc.prof_free.v.push_back(ev);
-    }
-    evs.v.clear();
-    if (total_out) *total_out = total;
-    if (cnt_out) *cnt_out = cnt;
+    HIPCHK(hipSetDevice(h->device));
+    h->sc.prof.on = on != 0;
+    if (on) HIPCHK(h->sc.prof.warm(256));
     return DPH_OK;
 }
 
@@ -1878,9 +1841,9 @@ int dph_profile_read(dph_index* h, double* scan_ms_total, int* scan_launches) {
     if (!h || !scan_ms_total || !scan_launches) return fail(DPH_E_ARG, "null");
     if (h->sh->pq) return dph_pq_profile_read(h->sh->pq, scan_ms_total, scan_launches);
     HIPCHK(hipSetDevice(h->device));
-    int rc = drain_events(h, h->sc.prof_events_ladder, nullptr, nullptr);
+    int rc = h->sc.prof.drain(h->sc.prof_events_ladder, nullptr, nullptr);
     if (rc) return rc;
-    return drain_events(h, h->sc.prof_events, scan_ms_total, scan_launches);
+    return h->sc.prof.drain(h->sc.prof_events, scan_ms_total, scan_launches);
 }
 
 // every bracketed launch since the last read on its own: which = 0 the full scans (PQ index: the coarse filter scans), 1 the ladder levels'
@@ -1888,15 +1851,15 @@ int dph_profile_read_each(dph_index* h, int which, double* ms_out, int cap, int*
     if (!h || !n_out || cap < 0 || (cap > 0 && !ms_out)) return fail(DPH_E_ARG, "dph_profile_read_each: bad arguments");
     if (h->sh->pq) return dph_pq_profile_read_each(h->sh->pq, ms_out, cap, n_out);
     HIPCHK(hipSetDevice(h->device));
-    return drain_events(h, which ? h->sc.prof_events_ladder : h->sc.prof_events, nullptr, n_out, ms_out, cap);
+    return h->sc.prof.drain(which ? h->sc.prof_events_ladder : h->sc.prof_events, nullptr, n_out, ms_out, cap);
 }
 
 int dph_profile_read_all(dph_index* h, double* scan_ms_total, int* scan_launches, double* ladder_ms_total, int* ladder_launches) {
     if (!h || !scan_ms_total || !scan_launches || !ladder_ms_total || !ladder_launches) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(h->device));
-    int rc = drain_events(h, h->sc.prof_events_ladder, ladder_ms_total, ladder_launches);
+    int rc = h->sc.prof.drain(h->sc.prof_events_ladder, ladder_ms_total, ladder_launches);
     if (rc) return rc;
-    return drain_events(h, h->sc.prof_events, scan_ms_total, scan_launches);
+    return h->sc.prof.drain(h->sc.prof_events, scan_ms_total, scan_launches);
 }
 
 // what the two scan hooks below share: the query rows copied and quantised, one pass over them (a list-major shard: every tile)
@@ -1953,18 +1916,15 @@ int dph_debug_scan_time(dph_index* h, const float* x, int64_t n, int iters, floa
     // a bound no high-digit score reaches (|H| <= 127 * 128 * 768 < 2^24 = (2^31 - 1 - lmax) >> 7 for any lmax < 2^24): the
     // launch streams and multiplies everything and emits nothing
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->sc.tau_dev, 0x7fffffff, (size_t)n, st));
-    hipEvent_t a = nullptr, b = nullptr;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
+    dph_profiler prof;                  // (of this call alone: one event pair, read back after every launch)
+    dph_event_pairs one;
     for (int i = 0; i < iters; ++i) {
-        HIPCHK(hipEventRecord(a, st));
-        dph_launch_scan(p, false, h->sh->n_tiles, 1, h->sc.tau_dev, st);
-        HIPCHK(hipEventRecord(b, st));
-        HIPCHK(hipEventSynchronize(b));
-        HIPCHK(hipEventElapsedTime(&ms_out[i], a, b));
+        prof.bracket(&one, st, [&] { dph_launch_scan(p, false, h->sh->n_tiles, 1, h->sc.tau_dev, st); });
+        double ms = 0.0;
+        rc = prof.drain(one, &ms, nullptr);
+        if (rc) return rc;
+        ms_out[i] = (float)ms;
     }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
     HIPCHK(hipGetLastError());
     return DPH_OK;
 }

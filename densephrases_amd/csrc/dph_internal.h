@@ -56,6 +56,50 @@ struct dph_event_pairs {
         return ev;
     }
 };
+// The profiler of a handle: while `on`, chosen launches run between an event pair of their own -- what a rocprofv3 kernel trace
+// reports per dispatch, so the two can be held against each other.  A bracketed launch leaves its pair in a list of the handle until
+// drain() reads that list and hands the pairs back to `idle`.
+struct dph_profiler {
+    bool on = false;
+    dph_event_pairs idle;
+    // create the events now: the first hipEventCreate of a process can take ~100 ms, and it must not land in a timed region
+    hipError_t warm(size_t n) {
+        while (idle.v.size() < n) {
+            std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+            hipError_t e = hipEventCreate(&ev.first);
+            if (e == hipSuccess) e = hipEventCreate(&ev.second);
+            if (e != hipSuccess) return e;
+            idle.v.push_back(ev);
+        }
+        return hipSuccess;
+    }
+    // `launch` between a (start, stop) pair that goes to `list`; list == NULL: the launch alone
+    template <typename Launch> void bracket(dph_event_pairs* list, hipStream_t st, Launch launch) {
+        std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+        if (list) { ev = idle.take(); (void)hipEventRecord(ev.first, st); }
+        launch();
+        if (list) { (void)hipEventRecord(ev.second, st); list->v.push_back(ev); }
+    }
+    // every bracketed launch of `list` since the last read: total and count, each duration to each_out[0 .. cap) when asked
+    int drain(dph_event_pairs& list, double* total_out, int* cnt_out, double* each_out = nullptr, int cap = 0) {
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+        evs.swap(list.v);               // back to `idle` first: a read that fails below leaves every pair with ONE owner
+        idle.v.insert(idle.v.end(), evs.begin(), evs.end());
+        double total = 0.0;
+        int cnt = 0;
+        for (auto& ev : evs) {
+            HIPCHK(hipEventSynchronize(ev.second));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
+            total += ms;
+            if (each_out && cnt < cap) each_out[cnt] = ms;
+            ++cnt;
+        }
+        if (total_out) *total_out = total;
+        if (cnt_out) *cnt_out = cnt;
+        return DPH_OK;
+    }
+};
 
 // Dynamic LDS beyond the default limit is granted per kernel and device: asked for once (`done`: a static of the call site -- zero-
 // initialised; handles are searched from several threads), asked again by the next call when it was refused.
@@ -351,8 +395,6 @@ void dph_launch_coarse(const dph_coarse_args& a, dph_coarse_scratch& s, hipStrea
 #define DPH_SCAN_X16 1
 #endif
 __host__ __device__ static inline bool dph_frag_x16(int aux_stride) { (void)aux_stride; return DPH_SCAN_X16 != 0; }
-// hands out a fresh (start, stop) event pair per bracketed launch (profiling; next == NULL: none)
-struct dph_event_source { void* ctx; void (*next)(void* ctx, hipEvent_t* a, hipEvent_t* b); };
 // long quantizers, the filter form: one-product bf16 GEMM with the threshold test in its epilogue (dph_ivf.hip).  A whole pass from row 0
 // (q0 = 0, no gate, no tiles); c_pk / x_pk feed its fail-over chain.
 struct dph_coarse_filter_args : dph_coarse_args {
@@ -363,7 +405,9 @@ struct dph_coarse_filter_args : dph_coarse_args {
     const float* cnorm = nullptr;       // [nlist] ||c_l||_2 (device)
     double cnorm_cap = 0.0;             // lists longer than this get exact scores
     int teams = 1;                      // variant 5, more than 128 rows: one launch of workgroup teams sharing tiles through L2 (dph_scan.hip MODE 4)
-    dph_event_source prof{nullptr, nullptr};
+    // profiling: an event pair of its own around EVERY launch of the filter's dominant kernel (the scan; the GEMM forms: the one GEMM
+    // launch), appended to prof_list.  Both NULL: none
+    dph_profiler* prof = nullptr; dph_event_pairs* prof_list = nullptr;
 };
 void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratch& s, hipStream_t st);
 void dph_launch_coarse_scan_teams(const void* img, int64_t n_lists, const void* qfrag, int n_q, int n_groups, const unsigned* est_keys, uint2* pairs,
@@ -426,6 +470,8 @@ int dph_list_major_sort(const int32_t* assign_dev, int64_t n, int nlist, uint64_
 void dph_launch_list_major_gather(const int8_t* src, const uint64_t* keys, int64_t n, const int64_t* src_start_dev,
                                   const int64_t* dst_start_dev, int64_t id_base, int8_t* dst, int64_t* row_ids,
                                   int32_t* inv_row, hipStream_t st);
+// (id, position) pairs sorted by id: the direct map of a PQ index
+int dph_sort_pairs_i64_u32(const int64_t* keys_in, const unsigned* vals_in, int64_t* keys_out, unsigned* vals_out, int64_t n, hipStream_t st);
 void dph_launch_fill(int8_t* db, int64_t n_rows, int64_t id_base, uint64_t seed, int kind, hipStream_t st);
 #define DPH_NORM_BINS 8192          // histogram of squared centred row norms: bins of DPH_NORM_BIN_W (max 768*168^2 < 2^25)
 #define DPH_NORM_BIN_W 4096u
@@ -462,12 +508,12 @@ const float* dph_pq_A_host(const dph_pq* p);
 void dph_pq_set_coarse_teams(dph_pq* p, int on);               // tuning key "coarse_teams"
 void dph_pq_set_coarse_filter(dph_pq* p, int on);              // tuning key "coarse_filter"
 void dph_pq_set_split_lut(dph_pq* p, int on);                  // tuning key "pq_split_lut"
-// measurement hook: HIP events around the coarse quantizer's dominant GEMM launch of every pass (dph_profile_enable / _read on a PQ index)
 int dph_pq_coarse_debug(dph_pq* p, unsigned out[2]);
 int dph_pq_coarse_debug_pool(dph_pq* p, unsigned* lk_host, unsigned short* q_host, long long cap, long long* count);
 int dph_pq_debug_phases(dph_pq* p, int which, unsigned long long* out, int cap);
 int dph_pq_debug_pass(dph_pq* p, int* info, unsigned* per_row, int n);
 int dph_coarse_select_clock(unsigned long long* out, int cap_rows);
+// measurement hook: HIP events around the coarse quantizer's dominant GEMM launch of every pass (dph_profile_enable / _read on a PQ index)
 int dph_pq_profile(dph_pq* p, int on);
 int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches);
 int dph_pq_profile_read_each(dph_pq* p, double* ms_out, int cap, int* n_out);

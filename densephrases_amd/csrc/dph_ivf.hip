@@ -1258,10 +1258,8 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
     const unsigned pool_cap = (unsigned)((size_t)n_q * CS_CAND);
     if (a.listmask) (void)hipMemsetAsync(a.listmask, 0, (size_t)nlist * a.mask_words * 4, st);       // (NULL: the caller walks probe_out only)
     (void)hipMemsetAsync(cnt, 0, sizeof *cnt, st);
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0 || cus > 256) cus = 256;           // (the wave statistics hold 256 CUs)
+    const int dev = dph_current_device();
+    const int cus = dph_scan_grid(dev);             // (at most 256: what the wave statistics hold)
     const size_t lds128 = (size_t)2 * CG_LISTS * (CF_K + 8) * 2;
     const size_t lds_v3 = (size_t)2 * CG_QROWS * (CF_K + 8) * 2 + (size_t)CF_HIT_CAP * 10;
     DPH_ALLOW_LDS(dph_coarse_filter_gemm_kernel<true>, lds128, dev);
@@ -1280,12 +1278,8 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
     hipLaunchKernelGGL(dph_coarse_filter_gemm_kernel<true>, dim3(std::min(tiles_s, wg), qt), dim3(256), lds128, st, n_q, m, stride, (int64_t)tiles_f, a.c_hi, a.x_hi,
                        f.sample.p, (const unsigned*)nullptr, (uint2*)nullptr, (unsigned short*)nullptr, (unsigned*)nullptr, 0u, (unsigned*)nullptr);
     hipLaunchKernelGGL(dph_coarse_estimate_sample_kernel, dim3(n_q), dim3(CS_THREADS), 0, st, f.sample.p, n_q, m, stride, target, est);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto bracket_begin = [&]() { ev0 = ev1 = nullptr; if (a.prof.next) { a.prof.next(a.prof.ctx, &ev0, &ev1); (void)hipEventRecord(ev0, st); } };
-    auto bracket_end = [&]() { if (ev1) (void)hipEventRecord(ev1, st); };
-    const bool scan = a.variant == 5 && a.c_pieces;
-    if (!scan) bracket_begin();
-    if (scan) {
+    auto profiled = [&](auto launch) { if (a.prof) a.prof->bracket(a.prof_list, st, launch); else launch(); };
+    if (a.variant == 5 && a.c_pieces) {
         // 128 query rows per read of the centroid image (one group of 32 per scan wave); a pass of more rows reads it once per 128 --
         // 4 x 0.27 ms against the GEMM's 1.36 ms at 512 rows.
         // More than 128 rows: ONE launch of teams (dph_scan.hip MODE 4) -- the groups of 128 rows share every tile through the XCDs' L2
@@ -1295,18 +1289,14 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
         const bool teams = a.teams != 0 && n_groups >= 2 && n_groups <= 8 && cus % (8 * n_groups) == 0;
         if (teams) {
             hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((n_groups * 4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi, n_q, f.qfrag.p, n_groups);
-            bracket_begin();
-            dph_launch_coarse_scan_teams(a.c_pieces, nlist, f.qfrag, n_q, n_groups, est, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st);
-            bracket_end();
+            profiled([&] { dph_launch_coarse_scan_teams(a.c_pieces, nlist, f.qfrag, n_q, n_groups, est, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st); });
             hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
                                n_q, 0u, f.cand.p, cand_cnt, (int)CS_CAND, pool_count, fail);
         }
         for (int q0 = 0; !teams && q0 < n_q; q0 += DPH_QROWS) {
             const int nq = std::min(n_q - q0, (int)DPH_QROWS);
             hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi + (int64_t)q0 * DPH_DIM, nq, f.qfrag.p);
-            bracket_begin();
-            dph_launch_coarse_scan(a.c_pieces, nlist, f.qfrag, nq, est + q0, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st);
-            bracket_end();
+            profiled([&] { dph_launch_coarse_scan(a.c_pieces, nlist, f.qfrag, nq, est + q0, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st); });
             // straight into the per-row candidate lists; DPH_CF_KEEP_POOL=1 (tools/debug_coarse_scan.py) writes the linear pool of the GEMM forms too
             static const bool keep_pool = getenv("DPH_CF_KEEP_POOL") && atoi(getenv("DPH_CF_KEEP_POOL")) != 0;
             if (keep_pool)
@@ -1315,17 +1305,18 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
             hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
                                n_q, (unsigned)q0, f.cand.p, cand_cnt, (int)CS_CAND, keep_pool ? &cnt->sink : pool_count, fail);
         }
-    } else if (a.variant >= 3 && a.c_frag)
-        hipLaunchKernelGGL(dph_coarse_filter_gemm2_kernel, dim3(std::min((nlist + CF2_LISTS - 1) / CF2_LISTS, std::max(1, cus / qt)), qt), dim3(CF2_THREADS), lds_v3, st,
-                           n_q, nlist, a.c_frag, a.x_hi, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail, a.variant == 4 ? 1 : 0);
-    else if (a.variant >= 2)
-        hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, true>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
-                           (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
-    else
-        hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, false>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
-                           (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
-    if (!scan) {
-        bracket_end();
+    } else {
+        profiled([&] {
+            if (a.variant >= 3 && a.c_frag)
+                hipLaunchKernelGGL(dph_coarse_filter_gemm2_kernel, dim3(std::min((nlist + CF2_LISTS - 1) / CF2_LISTS, std::max(1, cus / qt)), qt), dim3(CF2_THREADS), lds_v3, st,
+                                   n_q, nlist, a.c_frag, a.x_hi, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail, a.variant == 4 ? 1 : 0);
+            else if (a.variant >= 2)
+                hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, true>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
+                                   (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
+            else
+                hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, false>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
+                                   (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
+        });
         hipLaunchKernelGGL(dph_coarse_bucket_kernel, dim3(64), dim3(CB_THREADS), 0, st, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, n_q, f.cand.p, cand_cnt, (int)CS_CAND);
     }
     hipLaunchKernelGGL(dph_coarse_select_kernel, dim3(n_q), dim3(CS_THREADS), CS_LDS, st, a.x, 0, n_q, (const int*)nullptr, 0, a.centroids,

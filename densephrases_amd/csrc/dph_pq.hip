@@ -181,17 +181,11 @@ __global__ __launch_bounds__(256) void pq_transform_kernel(const float* __restri
     }
 }
 static constexpr size_t PQT_LDS = sizeof(double) * (PQT_ROWS * DPH_DIM + 2 * PQT_TB * PQT_COLS);       // 48 KiB + 64 KiB
-static int pq_launch_transform(const float* x, const float* At, int64_t n_rows, const float* b, float* out, unsigned short* out_hi, unsigned* out_pk,
-                               int device, hipStream_t st, int32_t* nonfinite = nullptr) {
-    static std::atomic<bool> attr[64];
-    if (device < 0 || device >= 64 || !attr[device]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)pq_transform_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQT_LDS);
-        if (e != hipSuccess) return 1;
-        if (device >= 0 && device < 64) attr[device] = true;
-    }
+static void pq_launch_transform(const float* x, const float* At, int64_t n_rows, const float* b, float* out, unsigned short* out_hi, unsigned* out_pk,
+                                int device, hipStream_t st, int32_t* nonfinite = nullptr) {
+    DPH_ALLOW_LDS(pq_transform_kernel, PQT_LDS, device);
     hipLaunchKernelGGL(pq_transform_kernel, dim3((unsigned)((n_rows + PQT_ROWS - 1) / PQT_ROWS), DPH_DIM / PQT_COLS), dim3(256), PQT_LDS, st, x, At, n_rows, b, out,
                        out_hi, out_pk, nonfinite);
-    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- LUT[r][m][j]
@@ -866,19 +860,37 @@ __global__ __launch_bounds__(256) void pq_dup_kernel(const int64_t* sorted_ids, 
 }
 
 // ============================================================================================== host side
-void dph_pq_free(dph_pq* p);
-int dph_sort_pairs_i64_u32(const int64_t* keys_in, const unsigned* vals_in, int64_t* keys_out, unsigned* vals_out, int64_t n, hipStream_t st);
+// head of the counters of a pass: the kernels get the addresses of its fields
+struct pq_pass_head {
+    int n_pairs;                                           // list-major scan: pair records written (pq_pairs_kernel)
+    int next;                                              // head of the work queue the scan workgroups pop (pairs or units)
+    int n_units;                                           // row-major scan: unit records written (pq_units_kernel)
+    int pad[13];
+};
+static_assert(sizeof(pq_pass_head) == 64 && offsetof(pq_pass_head, n_pairs) == 0 && offsetof(pq_pass_head, next) == 4 && offsetof(pq_pass_head, n_units) == 8,
+              "dph_pq_debug_pass hands the head's first words to Python as info[0..3] = pairs, items taken, units, -");
 
-// the per-pass scratch, sized by pq_ensure from (rows, k, nprobe) and the list lengths; released as a whole (`p->s = pq_scratch()`)
+// the per-pass scratch, sized by pq_ensure from (rows, k, nprobe) and the list lengths; released as a whole (`p->s = pq_scratch()`),
+// its description with it
 struct pq_scratch {
-    int cap_rows = 0;
+    int cap_rows = 0, cap_k = 0, cap_nprobe = 0;           // what it was sized for
+    int cand_cap = 0, pair_cap = 0, unit_cap = 0;          // candidates per row; pair and unit records per pass
     dev_buf<float> xp, lut, scores;
     dev_buf<unsigned> xp_pk;                               // bf16 hi << 16 | lo of the rotated query rows of a pass
     dev_buf<unsigned short> xp_hi;                         // ... and as plain bf16
     dev_buf<unsigned> listmask;
-    dev_buf<int2> pairs; dev_buf<int> counters; dev_buf<uint2> cand;
-    unsigned *bound = nullptr, *cand_count = nullptr, *overflow = nullptr;   // (live behind `counters`)
-    int32_t* nf = nullptr;                                 // [rows] query rows with a NaN / Inf element (pq_transform_kernel; lives behind `counters`)
+    dev_buf<int2> pairs; dev_buf<uint2> cand;
+    // the counters of a pass, ONE allocation: pq_pass_head | bound | cand_count | overflow | nf, the four arrays [cap_rows] words each
+    dev_buf<int> counters;
+    pq_pass_head* head() const { return (pq_pass_head*)counters.p; }
+    unsigned* row_words(int which) const { return (unsigned*)(counters.p + sizeof(pq_pass_head) / 4) + (size_t)which * cap_rows; }
+    unsigned* bound() const { return row_words(0); }
+    unsigned* cand_count() const { return row_words(1); }
+    unsigned* overflow() const { return row_words(2); }
+    int32_t* nf() const { return (int32_t*)row_words(3); } // query rows with a NaN / Inf element (pq_transform_kernel writes every row's)
+    // bytes of the head and the first `arrays` of them.  All four are allocated; one memset in front of every pass clears three (the
+    // coarse quantizer flags a row whose error band overflows in `overflow` too) -- not nf, which the transform has written by then
+    static size_t counter_bytes(int rows, int arrays) { return sizeof(pq_pass_head) + (size_t)arrays * rows * 4; }
     dev_buf<int> probe;                                    // [rows][nprobe] probed lists of every row (row-major scan)
     dev_buf<int2> units;                                   // ... and its work queue: (group, segment) records (pq_units_kernel)
 };
@@ -896,8 +908,8 @@ struct dph_pq {
                                                            // non-temporal), 3: centroids straight into registers from the fragment-major image, 4: 3 on contiguous tile runs,
                                                            // 5 (default, round 5): the filter as a SCAN -- bf16 centroid pieces through the flat scan's feed (dph_scan.hip MODE 3)
     int coarse_teams = 1;                                  // tuning key "coarse_teams": passes of more than 128 rows run the filter scan as ONE launch of workgroup teams
-    bool profile = false;
-    dph_event_pairs prof_events, prof_free;
+    dph_profiler prof;
+    dph_event_pairs prof_events;                           // around the launches of the coarse filter's dominant kernel
     std::vector<float> h_A;
     dev_buf<uint8_t> codes; dev_buf<int64_t> ids, list_off;
     std::vector<int64_t> h_list_off;
@@ -908,7 +920,6 @@ struct dph_pq {
     bool lists_set = false, params_set = false, finalized = false;
     // scratch, grown on demand
     pq_scratch s;
-    int cap_k = 0, cap_nprobe = 0, cand_cap = 0, pair_cap = 0, unit_cap = 0;
     std::vector<int64_t> h_top_prefix;                     // [i] = codes in the i longest lists: what a row can meet at most with nprobe = i
     // what lives until the index is freed
     dev_buf<float> qrot; int64_t qrot_rows = 0;            // rotated query halves of dph_pq_window
@@ -960,15 +971,16 @@ int dph_pq_debug_pass(dph_pq* p, int* info, unsigned* per_row, int n) {
     if (!p->s.counters) return fail(DPH_E_STATE, "PQ debug: no search yet");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(info, p->s.counters, 16, hipMemcpyDeviceToHost));
-    info[4] = p->cand_cap; info[5] = p->unit_cap; info[6] = p->pair_cap; info[7] = p->s.cap_rows;
+    pq_pass_head head;
+    HIPCHK(hipMemcpy(&head, p->s.head(), sizeof head, hipMemcpyDeviceToHost));
+    info[0] = head.n_pairs; info[1] = head.next; info[2] = head.n_units; info[3] = head.pad[0];
+    info[4] = p->s.cand_cap; info[5] = p->s.unit_cap; info[6] = p->s.pair_cap; info[7] = p->s.cap_rows;
     n = std::min(n, p->s.cap_rows);
-    std::vector<unsigned> a((size_t)n), b((size_t)n), c((size_t)n);
-    if (n > 0 && per_row) {
-        HIPCHK(hipMemcpy(a.data(), p->s.cand_count, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(b.data(), p->s.overflow, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c.data(), p->s.bound, (size_t)n * 4, hipMemcpyDeviceToHost));
-        for (int r = 0; r < n; ++r) { per_row[3 * r] = a[(size_t)r]; per_row[3 * r + 1] = b[(size_t)r]; per_row[3 * r + 2] = c[(size_t)r]; }
+    const unsigned* const cols[3] = {p->s.cand_count(), p->s.overflow(), p->s.bound()};
+    std::vector<unsigned> col((size_t)n);
+    for (int c = 0; c < 3 && n > 0 && per_row; ++c) {
+        HIPCHK(hipMemcpy(col.data(), cols[c], (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (int r = 0; r < n; ++r) per_row[3 * r + c] = col[(size_t)r];
     }
     return DPH_OK;
 }
@@ -980,8 +992,7 @@ int dph_pq_debug_phases(dph_pq* p, int which, unsigned long long* out, int cap_w
     if (hipSetDevice(p->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
     if (which == 1) return dph_coarse_select_clock(out, cap_wgs);        // the probe selection's stamps, one record per query row
     if (!p->phase_prof) {
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
+        const int cus = dph_scan_grid(p->device);
         if (p->phase_prof.alloc((size_t)cus * 8) != hipSuccess) return -1;
         (void)hipMemset(p->phase_prof, 0, (size_t)cus * 64);
         p->phase_wgs = cus;
@@ -993,49 +1004,19 @@ int dph_pq_debug_phases(dph_pq* p, int which, unsigned long long* out, int cap_w
 int dph_pq_profile(dph_pq* p, int on) {
     if (!p) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
-    p->profile = on != 0;
-    while (p->profile && p->prof_free.v.size() < 64) {
-        std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-        HIPCHK(hipEventCreate(&ev.first));
-        HIPCHK(hipEventCreate(&ev.second));
-        p->prof_free.v.push_back(ev);
-    }
+    p->prof.on = on != 0;
+    if (on) HIPCHK(p->prof.warm(64));
     return DPH_OK;
 }
 int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches) {
     if (!p || !ms_total || !launches) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
-    double total = 0.0;
-    int cnt = 0;
-    for (auto& ev : p->prof_events.v) {
-        HIPCHK(hipEventSynchronize(ev.second));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
-        total += ms;
-        ++cnt;
-        p->prof_free.v.push_back(ev);
-    }
-    p->prof_events.v.clear();
-    *ms_total = total;
-    *launches = cnt;
-    return DPH_OK;
+    return p->prof.drain(p->prof_events, ms_total, launches);
 }
-
 int dph_pq_profile_read_each(dph_pq* p, double* ms_out, int cap, int* n_out) {
     if (!p || !n_out) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
-    int n = 0;
-    for (auto& ev : p->prof_events.v) {
-        HIPCHK(hipEventSynchronize(ev.second));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
-        if (n < cap && ms_out) ms_out[n] = ms;
-        ++n;
-        p->prof_free.v.push_back(ev);
-    }
-    p->prof_events.v.clear();
-    *n_out = n;
-    return DPH_OK;
+    return p->prof.drain(p->prof_events, nullptr, n_out, ms_out, cap);
 }
 
 void dph_pq_free(dph_pq* p) {
@@ -1163,58 +1144,141 @@ int64_t dph_pq_ntotal(const dph_pq* p) { return p ? p->ntotal : 0; }
 int dph_pq_nlist(const dph_pq* p) { return p ? p->nlist : 0; }
 const float* dph_pq_A_host(const dph_pq* p) { return p ? p->h_A.data() : nullptr; }
 
-static int pq_seg(const dph_pq* p) { return p->M <= 96 ? PQ_SEG : PQ_SEG / 2; }
+static constexpr int pq_seg(int M) { return M <= 96 ? PQ_SEG : PQ_SEG / 2; }
 // many short lists ON AVERAGE: the work is grouped by query row (pq_adc_rows_kernel) and cut by code count, so a list hundreds of times
 // the mean is several units of several workgroups.  (A group's 64 lists are one sequence indexed with 32-bit ints: 2^24 codes per list.)
 static bool pq_by_rows(const dph_pq* p) { return p->ntotal / p->nlist < 2048 && p->max_list < ((int64_t)1 << 24); }
+// codes a query row can meet at most: those of its nprobe LONGEST lists, not nprobe x the longest (dph_pq_set_list_sizes fills the
+// prefix sums, and no index is searched without it)
+static int64_t pq_row_codes_max(const dph_pq* p, int nprobe) { return p->h_top_prefix[(size_t)std::min(nprobe, p->nlist)]; }
 // units / segments a query row can meet at most: one (partial) segment per group + the codes of its nprobe longest lists cut into segments
-static int64_t pq_row_units_max(const dph_pq* p, int nprobe) {
-    const int np_ = std::min(nprobe, p->nlist);
-    const int64_t top = p->h_top_prefix.empty() ? p->ntotal : p->h_top_prefix[(size_t)np_];
-    return (nprobe + PQ_GROUP - 1) / PQ_GROUP + top / pq_seg(p) + 1;
+static int64_t pq_row_units_max(const dph_pq* p, int nprobe) { return (nprobe + PQ_GROUP - 1) / PQ_GROUP + pq_row_codes_max(p, nprobe) / pq_seg(p->M) + 1; }
+// dynamic LDS of the ADC scans: the row's tables [M][256], the keys of a segment, histogram, wave partials, the queue item
+static constexpr size_t pq_lds_bytes(int M) { return (size_t)M * 1024 + (size_t)pq_seg(M) * 4 + 264 * 4 + 16 * 8 + 16; }
+// ... and the most any M that dph_pq_alloc accepts asks for: the allowance is granted once per kernel and device, whatever the handle
+static constexpr size_t pq_lds_bytes_max() {
+    size_t mx = 0;
+    for (int M = 16; M <= 128; M += 16) if (DPH_DIM % M == 0 && pq_lds_bytes(M) > mx) mx = pq_lds_bytes(M);
+    return mx;
 }
-static size_t pq_lds_bytes(const dph_pq* p) { return (size_t)p->M * 1024 + (size_t)pq_seg(p) * 4 + 264 * 4 + 16 * 8 + 16; }
+static_assert(pq_lds_bytes_max() <= 160 * 1024, "the ADC scans' tables and keys must fit the 160 KiB of LDS of a CU");
+// (one workgroup per CU either way: __launch_bounds__(PQ_THREADS, 1); the launches pass pq_lds_bytes(p->M))
+static void pq_allow_lds(int device) {
+    DPH_ALLOW_LDS(pq_adc_kernel<6>, pq_lds_bytes_max(), device);
+    DPH_ALLOW_LDS(pq_adc_kernel<8>, pq_lds_bytes_max(), device);
+    DPH_ALLOW_LDS(pq_adc_rows_kernel<6>, pq_lds_bytes_max(), device);
+    DPH_ALLOW_LDS(pq_adc_rows_kernel<8>, pq_lds_bytes_max(), device);
+}
 
 static int pq_ensure(dph_pq* p, int rows, int k, int nprobe) {
-    if (rows <= p->s.cap_rows && k <= p->cap_k && nprobe <= p->cap_nprobe) return DPH_OK;
-    rows = std::max(rows, p->s.cap_rows); k = std::max(k, p->cap_k); nprobe = std::max(nprobe, p->cap_nprobe);
+    if (rows <= p->s.cap_rows && k <= p->s.cap_k && nprobe <= p->s.cap_nprobe) return DPH_OK;
+    rows = std::max(rows, p->s.cap_rows); k = std::max(k, p->s.cap_k); nprobe = std::max(nprobe, p->s.cap_nprobe);
     p->s = pq_scratch();
+    pq_scratch& s = p->s;
     // every segment may append its k best -- or, in the row-major scan (pq_segment_finish<true>: the bound of a long segment is the k-th of
     // a 1024-key sample), about k * seg / 1024 keys: twice that is reserved
     const bool by_rows = pq_by_rows(p);
     // (the scratch serves every later call with k' <= k without a new allocation: the sampled rule's share for min(k, 128) counts even when
     // THIS k is beyond it)
-    const int64_t per_seg = by_rows ? std::max<int64_t>(k, (int64_t)std::min(k, PQ_THREADS / 8) * (pq_seg(p) / PQ_THREADS) * 2) : k;
-    // segments a row can meet: row-major, (partial) segments of its groups -- from the nprobe LONGEST lists, not nprobe x the longest;
-    // list-major, every probed list on its own
-    const int64_t segs_row = by_rows ? pq_row_units_max(p, nprobe) : (int64_t)nprobe + (p->h_top_prefix.empty() ? p->ntotal : p->h_top_prefix[(size_t)std::min(nprobe, p->nlist)]) / pq_seg(p);
+    const int64_t per_seg = by_rows ? std::max<int64_t>(k, (int64_t)std::min(k, PQ_THREADS / 8) * (pq_seg(p->M) / PQ_THREADS) * 2) : k;
+    // segments a row can meet: row-major, (partial) segments of its groups; list-major, every probed list on its own
+    const int64_t codes_row = pq_row_codes_max(p, nprobe);
+    const int64_t segs_row = by_rows ? pq_row_units_max(p, nprobe) : (int64_t)nprobe + codes_row / pq_seg(p->M);
     // + 512: the count above the k-th of a 1-in-12 sample has a geometric tail -- for k = 1, P(more than m) = (11/12)^m: m = 64 was
     // crossed once in 4000 cold segments, 512 once in 10^19
     int64_t cap = segs_row * per_seg + 512;
     const int64_t budget = ((int64_t)2 << 30) / 8 / rows;                // at most 2 GiB of candidates per pass
     cap = std::max<int64_t>(std::min(cap, budget), 4 * (int64_t)k + 64);
-    p->cand_cap = (int)std::min<int64_t>(cap, 1 << 30);
+    s.cand_cap = (int)std::min<int64_t>(cap, 1 << 30);
     // list-major pairs: one per chunk of PQ_LM_CHUNK segments of a probed list -- at most nprobe + (codes of the nprobe longest lists) / chunk per row
-    p->pair_cap = (int)std::min<int64_t>((int64_t)rows * (nprobe + (by_rows ? 0 : (p->h_top_prefix.empty() ? p->ntotal : p->h_top_prefix[(size_t)std::min(nprobe, p->nlist)]) / ((int64_t)pq_seg(p) * PQ_LM_CHUNK))), 1 << 28);
-    p->unit_cap = by_rows ? (int)std::min<int64_t>((int64_t)rows * pq_row_units_max(p, nprobe), 1 << 28) : 0;
-    if (p->s.xp.alloc((size_t)rows * DPH_DIM) != hipSuccess || p->s.lut.alloc((size_t)rows * p->M * 256) != hipSuccess ||
-        p->s.scores.alloc((size_t)rows * p->nlist) != hipSuccess || p->s.listmask.alloc((size_t)p->nlist * DPH_UNIT_WORDS) != hipSuccess ||
-        p->s.counters.alloc(16 + (size_t)4 * rows) != hipSuccess ||        // counters | bound | cand_count | overflow (one memset per pass) | non-finite flags
-        p->s.pairs.alloc((size_t)p->pair_cap) != hipSuccess ||
-        p->s.cand.alloc((size_t)rows * p->cand_cap) != hipSuccess ||
-        p->s.probe.alloc((size_t)rows * nprobe) != hipSuccess ||
-        (p->unit_cap > 0 && p->s.units.alloc((size_t)p->unit_cap) != hipSuccess) ||
-        p->s.xp_pk.alloc((size_t)rows * DPH_DIM) != hipSuccess ||
-        p->s.xp_hi.alloc((size_t)rows * DPH_DIM) != hipSuccess) {
+    s.pair_cap = (int)std::min<int64_t>((int64_t)rows * (nprobe + (by_rows ? 0 : codes_row / ((int64_t)pq_seg(p->M) * PQ_LM_CHUNK))), 1 << 28);
+    s.unit_cap = by_rows ? (int)std::min<int64_t>((int64_t)rows * pq_row_units_max(p, nprobe), 1 << 28) : 0;
+    if (s.xp.alloc((size_t)rows * DPH_DIM) != hipSuccess || s.lut.alloc((size_t)rows * p->M * 256) != hipSuccess ||
+        s.scores.alloc((size_t)rows * p->nlist) != hipSuccess || s.listmask.alloc((size_t)p->nlist * DPH_UNIT_WORDS) != hipSuccess ||
+        s.counters.alloc(pq_scratch::counter_bytes(rows, 4) / 4) != hipSuccess ||
+        s.pairs.alloc((size_t)s.pair_cap) != hipSuccess ||
+        s.cand.alloc((size_t)rows * s.cand_cap) != hipSuccess ||
+        s.probe.alloc((size_t)rows * nprobe) != hipSuccess ||
+        (s.unit_cap > 0 && s.units.alloc((size_t)s.unit_cap) != hipSuccess) ||
+        s.xp_pk.alloc((size_t)rows * DPH_DIM) != hipSuccess ||
+        s.xp_hi.alloc((size_t)rows * DPH_DIM) != hipSuccess) {
         p->s = pq_scratch();
         return fail(DPH_E_NOMEM, "PQ search: scratch allocation failed");
     }
-    p->s.bound = (unsigned*)(p->s.counters + 16);
-    p->s.cand_count = p->s.bound + rows;
-    p->s.overflow = p->s.cand_count + rows;
-    p->s.nf = (int32_t*)(p->s.overflow + rows);
-    p->s.cap_rows = rows; p->cap_k = k; p->cap_nprobe = nprobe;
+    s.cap_rows = rows; s.cap_k = k; s.cap_nprobe = nprobe;
     return DPH_OK;
+}
+
+// ---- a pass of up to DPH_PASS_MAX query rows in four stages, all asynchronous on st
+// Stage 1: the rows rotated, x' = A x + b (a long quantizer: with their bf16 images), and their inner-product tables.
+static void pq_pass_tables(dph_pq* p, const float* x, int nq, hipStream_t st) {
+    pq_launch_transform(x, p->At, nq, p->b, p->s.xp, p->cent_pk ? p->s.xp_hi : (unsigned short*)nullptr, p->cent_pk ? p->s.xp_pk : (unsigned*)nullptr, p->device, st, p->s.nf());
+    const dim3 lg(nq, (p->M + 7) / 8);
+    if (p->dsub == 8) hipLaunchKernelGGL(pq_lut_kernel<8>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);             // M = 96 (the released OPQ96)
+    else if (p->dsub == 12) hipLaunchKernelGGL(pq_lut_kernel<12>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);       // M = 64
+    else if (p->dsub == 16) hipLaunchKernelGGL(pq_lut_kernel<16>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);       // M = 48
+    else hipLaunchKernelGGL(pq_lut_kernel<0>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);
+}
+
+// what the coarse quantizer is asked for a pass: probe masks per list (list-major scan) or a probe list per row -- the row-major scan
+// walks the probe lists, not the masks (134 MB to clear at 2^20 lists)
+static dph_coarse_filter_args pq_coarse_args(dph_pq* p, int nq, int nprobe, bool by_rows) {
+    dph_coarse_filter_args c;
+    c.x = p->s.xp; c.n_q = nq;
+    c.centroids = p->cent; c.nlist = p->nlist; c.nprobe = nprobe; c.cnorm_max = p->cnorm_max;
+    c.scores = p->s.scores;
+    c.listmask = by_rows ? nullptr : p->s.listmask.p; c.mask_words = DPH_UNIT_WORDS;
+    c.probe_out = by_rows ? p->s.probe.p : nullptr; c.probe_stride = nprobe;
+    c.c_pk = p->cent_pk; c.x_pk = p->cent_pk ? p->s.xp_pk.p : nullptr;
+    c.row_fail = p->s.overflow();
+    // the filter form's part
+    c.c_hi = p->cent_hi; c.x_hi = p->s.xp_hi; c.c_frag = p->cent_frag; c.c_pieces = p->cent_pieces;
+    c.cnorm = p->cnorm; c.cnorm_cap = p->cnorm_cap;
+    c.variant = p->coarse_filter; c.teams = p->coarse_teams;
+    if (p->prof.on) { c.prof = &p->prof; c.prof_list = &p->prof_events; }
+    return c;
+}
+// Stage 2: the counters of the pass cleared, then the coarse probe -- a long quantizer through the filter form, otherwise the chain.
+static int pq_pass_probe(dph_pq* p, int nq, int nprobe, bool by_rows, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(p->s.counters, 0, pq_scratch::counter_bytes(p->s.cap_rows, 3), st));
+    const dph_coarse_filter_args c = pq_coarse_args(p, nq, nprobe, by_rows);
+    if (p->cent_hi && p->coarse_filter) dph_launch_coarse_filter(c, p->coarse, st);
+    else dph_launch_coarse(c, p->coarse, st);
+    return DPH_OK;
+}
+
+template <int NG> static void pq_launch_adc(const dph_pq* p, const pq_scan_args& a, bool by_rows, int grid, int nprobe, int units_per_row, hipStream_t st) {
+    if (by_rows) hipLaunchKernelGGL(pq_adc_rows_kernel<NG>, dim3(grid), dim3(PQ_THREADS), pq_lds_bytes(p->M), st, a, p->s.probe, nprobe, units_per_row);
+    else hipLaunchKernelGGL(pq_adc_kernel<NG>, dim3(grid), dim3(PQ_THREADS), pq_lds_bytes(p->M), st, a);
+}
+// Stage 3: the work queue from what the probe left (units of a row's groups, or (list, row) pairs), then the ADC scan, one workgroup per CU.
+static void pq_pass_scan(dph_pq* p, int nq, int k, int nprobe, bool by_rows, int grid, hipStream_t st) {
+    const pq_scratch& s = p->s;
+    pq_pass_head* const head = s.head();           // (addresses of device memory: nothing is read here)
+    pq_scan_args a;
+    a.xp = s.xp; a.cent = p->cent; a.lut = s.lut; a.codes = p->codes; a.list_off = p->list_off;
+    a.pairs = s.pairs; a.n_pairs = &head->n_pairs; a.next = &head->next; a.pair_cap = s.pair_cap;
+    a.M = p->M; a.seg = pq_seg(p->M); a.k = k; a.by_residual = p->by_residual;
+    a.bound = s.bound(); a.cand_count = s.cand_count(); a.cand = s.cand; a.cand_cap = s.cand_cap; a.overflow = s.overflow();
+    a.prof = p->phase_prof && p->phase_wgs >= grid ? p->phase_prof : nullptr;
+    a.split_lut = p->split_lut;
+    a.units = s.units; a.n_units = &head->n_units; a.unit_cap = s.unit_cap;
+    const int upr = (nprobe + PQ_GROUP - 1) / PQ_GROUP;
+    // many short lists on average: group the work by query row, cut by code count (pq_units_kernel)
+    if (by_rows)
+        hipLaunchKernelGGL(pq_units_kernel, dim3((nq * upr + 3) / 4), dim3(256), 0, st, s.probe, nprobe, upr, nq * upr, p->list_off, a.seg, s.units,
+                           &head->n_units, s.unit_cap, s.overflow());
+    else
+        hipLaunchKernelGGL(pq_pairs_kernel, dim3((p->nlist + 255) / 256), dim3(256), 0, st, s.listmask, DPH_UNIT_WORDS, p->nlist,
+                           p->list_off, a.seg, s.pairs, &head->n_pairs, s.pair_cap, s.overflow());
+    if (p->M <= 96) pq_launch_adc<6>(p, a, by_rows, grid, nprobe, upr, st);
+    else pq_launch_adc<8>(p, a, by_rows, grid, nprobe, upr, st);
+}
+
+// Stage 4: every row's k best candidates, their ids and the row's status.
+static void pq_pass_final(dph_pq* p, int q0, int nq, int k, float* D, int64_t* I, int32_t* status, hipStream_t st) {
+    hipLaunchKernelGGL(pq_final_kernel, dim3(nq), dim3(PQ_THREADS), 0, st, p->s.cand, p->s.cand_count(), p->s.cand_cap, p->s.overflow(), p->ids,
+                       q0, k, D, I, status, (const int32_t*)p->s.nf());
 }
 
 // x_dev [n,768] -> D/I [n,k], status [n] (0 = exact top-k of the probed lists, 1 = candidate buffers overflowed); asynchronous on st
@@ -1222,95 +1286,33 @@ int dph_pq_search_dev(dph_pq* p, const float* x_dev, int64_t n, int k, int nprob
     if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ search: index not finalized");
     HIPCHK(hipSetDevice(p->device));
     nprobe = std::max(1, std::min(nprobe, p->nlist));
-    const int pass = (int)std::min<int64_t>(n, DPH_PASS_MAX);
-    int rc = pq_ensure(p, pass, k, nprobe);
+    int rc = pq_ensure(p, (int)std::min<int64_t>(n, DPH_PASS_MAX), k, nprobe);
     if (rc) return rc;
-    static std::atomic<size_t> attr_bytes[64];                // dynamic LDS the kernel is allowed on that device so far
-    if (p->device >= 64 || attr_bytes[p->device] < pq_lds_bytes(p)) {
-        hipError_t e = hipSuccess;
-        const void* ks[4] = {(const void*)pq_adc_kernel<6>, (const void*)pq_adc_kernel<8>, (const void*)pq_adc_rows_kernel<6>, (const void*)pq_adc_rows_kernel<8>};
-        for (const void* kf : ks) if (e == hipSuccess) e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pq_lds_bytes(p));
-        if (e != hipSuccess) return fail(DPH_E_HIP, std::string("PQ search: hipFuncSetAttribute: ") + hipGetErrorString(e));
-        if (p->device < 64) attr_bytes[p->device] = pq_lds_bytes(p);
-    }
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
+    pq_allow_lds(p->device);
+    const int grid = dph_scan_grid(p->device);
+    const bool by_rows = pq_by_rows(p);
     for (int64_t q0 = 0; q0 < n; q0 += DPH_PASS_MAX) {
         const int nq = (int)std::min<int64_t>(n - q0, DPH_PASS_MAX);
-        if (pq_launch_transform(x_dev + q0 * DPH_DIM, p->At, nq, p->b, p->s.xp, p->cent_pk ? p->s.xp_hi : (unsigned short*)nullptr, p->cent_pk ? p->s.xp_pk : (unsigned*)nullptr, p->device, st, p->s.nf))
-            return fail(DPH_E_HIP, "PQ search: hipFuncSetAttribute(pq_transform_kernel)");
-        {
-            const dim3 lg(nq, (p->M + 7) / 8);
-            if (p->dsub == 8) hipLaunchKernelGGL(pq_lut_kernel<8>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);             // M = 96 (the released OPQ96)
-            else if (p->dsub == 12) hipLaunchKernelGGL(pq_lut_kernel<12>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);       // M = 64
-            else if (p->dsub == 16) hipLaunchKernelGGL(pq_lut_kernel<16>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);       // M = 48
-            else hipLaunchKernelGGL(pq_lut_kernel<0>, lg, dim3(256), 0, st, p->s.xp, p->pqc, p->M, p->dsub, p->s.lut);
-        }
-        // many short lists on average: group the work by query row, cut by code count (pq_units_kernel)
-        const bool by_rows = pq_by_rows(p);
-        HIPCHK(hipMemsetAsync(p->s.counters, 0, 64 + (size_t)3 * p->s.cap_rows * 4, st));      // counters, bounds, candidate counts, overflow flags (the coarse
-                                                                                          // quantizer flags a row whose error band overflows there too)
-        unsigned* const lmask = by_rows ? nullptr : p->s.listmask;       // the row-major scan walks the probe lists, not the masks (134 MB to clear at 2^20 lists)
-        dph_coarse_filter_args c;
-        c.x = p->s.xp; c.n_q = nq;
-        c.centroids = p->cent; c.nlist = p->nlist; c.nprobe = nprobe; c.cnorm_max = p->cnorm_max;
-        c.scores = p->s.scores;
-        c.listmask = lmask; c.mask_words = DPH_UNIT_WORDS;
-        c.probe_out = by_rows ? p->s.probe.p : nullptr; c.probe_stride = nprobe;
-        c.c_pk = p->cent_pk; c.x_pk = p->cent_pk ? p->s.xp_pk.p : nullptr;
-        c.row_fail = p->s.overflow;
-        if (p->cent_hi && p->coarse_filter) {
-            c.c_hi = p->cent_hi; c.x_hi = p->s.xp_hi; c.c_frag = p->cent_frag; c.c_pieces = p->cent_pieces;
-            c.cnorm = p->cnorm; c.cnorm_cap = p->cnorm_cap;
-            c.variant = p->coarse_filter; c.teams = p->coarse_teams;
-            // profiling: an event pair of its own around EVERY launch of the filter's dominant kernel (the scan; the GEMM forms: the one
-            // GEMM launch) -- what a rocprofv3 kernel trace reports per dispatch, so the two can be held against each other
-            if (p->profile) {
-                c.prof.ctx = p;
-                c.prof.next = [](void* ctx, hipEvent_t* a, hipEvent_t* b) {
-                    dph_pq* q = (dph_pq*)ctx;
-                    const std::pair<hipEvent_t, hipEvent_t> ev = q->prof_free.take();
-                    q->prof_events.v.push_back(ev);
-                    *a = ev.first; *b = ev.second;
-                };
-            }
-            dph_launch_coarse_filter(c, p->coarse, st);
-        }
-        else
-            dph_launch_coarse(c, p->coarse, st);
-        pq_scan_args a;
-        a.xp = p->s.xp; a.cent = p->cent; a.lut = p->s.lut; a.codes = p->codes; a.list_off = p->list_off;
-        a.pairs = p->s.pairs; a.n_pairs = p->s.counters + 0; a.next = p->s.counters + 1; a.pair_cap = p->pair_cap;
-        a.M = p->M; a.seg = pq_seg(p); a.k = k; a.by_residual = p->by_residual;
-        a.bound = p->s.bound; a.cand_count = p->s.cand_count; a.cand = p->s.cand; a.cand_cap = p->cand_cap; a.overflow = p->s.overflow;
-        a.prof = p->phase_prof && p->phase_wgs >= cus ? p->phase_prof : nullptr;
-        a.split_lut = p->split_lut;
-        a.units = p->s.units; a.n_units = p->s.counters + 2; a.unit_cap = p->unit_cap;
-        if (by_rows) {
-            const int upr = (nprobe + PQ_GROUP - 1) / PQ_GROUP;
-            hipLaunchKernelGGL(pq_units_kernel, dim3((nq * upr + 3) / 4), dim3(256), 0, st, p->s.probe, nprobe, upr, nq * upr, p->list_off, a.seg, p->s.units,
-                               p->s.counters + 2, p->unit_cap, p->s.overflow);
-            if (p->M <= 96) hipLaunchKernelGGL(pq_adc_rows_kernel<6>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a, p->s.probe, nprobe, upr);
-            else hipLaunchKernelGGL(pq_adc_rows_kernel<8>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a, p->s.probe, nprobe, upr);
-        } else {
-            hipLaunchKernelGGL(pq_pairs_kernel, dim3((p->nlist + 255) / 256), dim3(256), 0, st, p->s.listmask, DPH_UNIT_WORDS, p->nlist,
-                               p->list_off, a.seg, p->s.pairs, p->s.counters + 0, p->pair_cap, p->s.overflow);
-            if (p->M <= 96) hipLaunchKernelGGL(pq_adc_kernel<6>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a);
-            else hipLaunchKernelGGL(pq_adc_kernel<8>, dim3(cus), dim3(PQ_THREADS), pq_lds_bytes(p), st, a);
-        }
-        hipLaunchKernelGGL(pq_final_kernel, dim3(nq), dim3(PQ_THREADS), 0, st, p->s.cand, p->s.cand_count, p->cand_cap, p->s.overflow, p->ids,
-                           (int)q0, k, D, I, status, (const int32_t*)p->s.nf);
+        pq_pass_tables(p, x_dev + q0 * DPH_DIM, nq, st);
+        rc = pq_pass_probe(p, nq, nprobe, by_rows, st);
+        if (rc) return rc;
+        pq_pass_scan(p, nq, k, nprobe, by_rows, grid, st);
+        pq_pass_final(p, (int)q0, nq, k, D, I, status, st);
     }
     HIPCHK(hipGetLastError());
     return DPH_OK;
+}
+
+// the stored index as the reconstruct / window kernels read it
+static pq_store pq_store_of(const dph_pq* p) {
+    return pq_store{p->cent, p->pqc, p->codes, p->list_off, p->dm_ids, p->dm_pos, p->ntotal, p->nlist, p->M, p->dsub, p->by_residual};
 }
 
 int dph_pq_reconstruct_dev(dph_pq* p, const int64_t* ids_dev, int64_t n, float* out_dev, int32_t* found_dev, hipStream_t st) {
     if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ reconstruct: index not finalized");
     HIPCHK(hipSetDevice(p->device));
     if (n <= 0) return DPH_OK;
-    pq_store s{p->cent, p->pqc, p->codes, p->list_off, p->dm_ids, p->dm_pos, p->ntotal, p->nlist, p->M, p->dsub, p->by_residual};
-    hipLaunchKernelGGL(pq_reconstruct_kernel, dim3((unsigned)n), dim3(256), 0, st, s, ids_dev, n, out_dev, found_dev);
+    hipLaunchKernelGGL(pq_reconstruct_kernel, dim3((unsigned)n), dim3(256), 0, st, pq_store_of(p), ids_dev, n, out_dev, found_dev);
     HIPCHK(hipGetLastError());
     return DPH_OK;
 }
@@ -1327,10 +1329,9 @@ int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf,
         HIPCHK(p->qrot.alloc((size_t)n_q * DPH_DIM));
         p->qrot_rows = n_q;
     }
-    if (pq_launch_transform(qhalf, p->At, n_q, nullptr, p->qrot, nullptr, nullptr, p->device, st)) return fail(DPH_E_HIP, "PQ window: hipFuncSetAttribute(pq_transform_kernel)");
-    pq_store s{p->cent, p->pqc, p->codes, p->list_off, p->dm_ids, p->dm_pos, p->ntotal, p->nlist, p->M, p->dsub, p->by_residual};
+    pq_launch_transform(qhalf, p->At, n_q, nullptr, p->qrot, nullptr, nullptr, p->device, st);
     const int64_t n_cand = n_q * k;
-    hipLaunchKernelGGL(pq_window_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, s, idmap, p->qrot, n_cand, k, L,
+    hipLaunchKernelGGL(pq_window_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, pq_store_of(p), idmap, p->qrot, n_cand, k, L,
                        ids, doc, word, first, row2doc, row2word, doc_ids, n_docs, f2o_off, f2o, pred_word, best, argslot, vecs);
     if (vecs && p->A) hipLaunchKernelGGL(pq_unrotate_kernel, dim3((unsigned)(2 * n_cand)), dim3(256), 0, st, vecs, p->A, 2 * n_cand);
     HIPCHK(hipGetLastError());
