@@ -756,8 +756,7 @@ __global__ __launch_bounds__(256) void pq_window_kernel(
     const int64_t c = (int64_t)blockIdx.x * 4 + (tid >> 6);
     if (c >= n_cand) return;
     const int64_t id = ids[c];
-    int64_t lc = dph_local_of_id(idmap, id);
-    const bool mine = lc >= 0;          // range-sharded: a candidate of another rank (FAISS padding, single rank: an unknown id)
+    int64_t lc = dph_local_of_id(idmap, id);          // idx2id is indexed by the LOCAL id (ownership is the direct map's, see `vecs` below)
     if (lc < 0) {
         const int64_t first_id = idmap.n_groups ? idmap.id_offsets[0] : idmap.id_base;
         lc = id < first_id ? 0 : idmap.n_ids - 1;
@@ -818,12 +817,15 @@ __global__ __launch_bounds__(256) void pq_window_kernel(
         // rotated-space vectors for now: [c,0,:] the candidate's own, [c,1,:] the arg-max slot's; pq_unrotate_kernel finishes them
         const int bi = direction == 0 ? best_slot : (L - 1 - best_slot);
         const int64_t idv[2] = {id, direction == 0 ? id + bi : id - bi};
+        // The shard holds a candidate when its DIRECT MAP does (what dph_reconstruct answers), whatever the id map says: ids of a PQ
+        // shard without id groups are sparse or offset (n_ids = ntotal, id_base = 0), and dph_local_of_id knows none of them.
+        // A candidate this shard does not hold contributes ZERO vectors, also for a window slot that happens to lie in this shard's
+        // range (the first rows of the next rank's range): the ranks' vectors are SUMMED (index.py _window_vectors), exactly one
+        // rank -- the candidate's, the only one that uploaded its code -- may speak
+        const int64_t own_pos = pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, id);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            // a candidate this shard does not hold contributes ZERO vectors, also for a window slot that happens to lie in this shard's
-            // range (the first rows of the next rank's range): the ranks' vectors are SUMMED (index.py _window_vectors), exactly one
-            // rank -- the candidate's -- may speak
-            const int64_t pos = mine ? pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, idv[t]) : -1;
+            const int64_t pos = t == 0 ? own_pos : (own_pos >= 0 ? pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, idv[t]) : -1);
             const int list = pos >= 0 ? pq_list_of_pos(s.list_off, s.nlist, pos) : 0;
             float* o = vecs + (c * 2 + t) * DPH_DIM + lane * 12;
 #pragma unroll

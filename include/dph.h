@@ -260,7 +260,13 @@ int dph_id2docword(dph_index* h, const int64_t* I, int64_t n, int32_t* doc, int3
  * the shard count as zero vectors (reconstruct failure, :285-288); valid = valid_phrase(:305-321) from the
  * f2o CSR.  Outputs: pred_word[c] = word of the arg-max slot or -1, best[c] = max score (double),
  * argslot[c]; if vecs != NULL, vecs[c,0,:] = candidate's own de-quantised row and vecs[c,1,:] = the
- * arg-max slot's row (fp32, [n,2,768]) for return_idxs (:381-389).  Host pointers, synchronous. */
+ * arg-max slot's row (fp32, [n,2,768]) for return_idxs (:381-389).  Host pointers, synchronous.
+ * Who holds a candidate: both vectors are ZERO for a candidate the shard does not hold, even when a slot of its
+ * window lies in the shard (the ranks of a range-sharded job SUM their vectors: only the candidate's own rank
+ * speaks).  A raw-dump shard holds the ids of its id map (id_base + row, or the id groups); a PQ shard holds the
+ * ids of its direct map -- the ids uploaded with its codes, what dph_reconstruct answers -- whatever the id map
+ * says (sparse or offset ids without id groups are held).  The idx2id lookup of a NULL doc / word goes through
+ * the id map on both: the local id, clipped into [0, n_ids). */
 int dph_rescore(dph_index* h, int direction, const float* qhalf /*[n_q,768]*/, int64_t n_q, int k, int L,
                 const int64_t* ids, const int32_t* doc, const int32_t* word, const float* first,
                 int32_t* pred_word, double* best, int32_t* argslot, float* vecs);

@@ -14,6 +14,7 @@ import pytest
 from densephrases_amd import faiss_io as F
 from oracle import ivfpq_oracle as P
 from tests._golden import GOLD, compare_results, load_toy_docs
+from tests._pq_build import _random_index, _shard  # noqa: F401  (other test files import them from here)
 
 PY39 = "/opt/conda/bin/python3.9"
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -35,18 +36,6 @@ def _pq_cases():
     for c in cases:
         c["query_arr"] = z[f"query_{c['query']}"]
     return cases, z["vecs"]
-
-
-def _random_index(seed, n, nlist, M=96, id_offset=0, dup=0):
-    rng = np.random.default_rng(seed)
-    centres = rng.normal(0, 0.5, (max(4, nlist // 2), 768)).astype(np.float32)
-    xb = (centres[rng.integers(0, len(centres), n)] + rng.normal(0, 0.3, (n, 768))).astype(np.float32)
-    if dup:
-        xb[rng.choice(n, dup, replace=False)] = xb[0]               # identical vectors -> identical codes -> score ties
-    ix = P.train(xb[: min(n, 3000)], nlist=nlist, M=M, seed=seed + 1)
-    ids = np.arange(n, dtype=np.int64) + id_offset
-    P.add_with_ids(ix, xb, ids)
-    return ix, xb, rng
 
 
 # ------------------------------------------------------------------------------------------------- CPU: format + oracle
@@ -164,16 +153,6 @@ def test_oracle_adc_search_agrees_with_brute_force_over_reconstructions():
 
 
 # ------------------------------------------------------------------------------------------------- GPU: kernels vs oracle
-def _shard(ix):
-    from densephrases_amd import Shard
-    s = Shard.from_faiss_index(ix, device=0)
-    n = s.ntotal
-    s.set_idx2id(np.zeros(n, np.int32), np.arange(n, dtype=np.int32))
-    s.set_f2o(np.zeros(1, np.int32), np.asarray([0, n], np.int64), np.arange(n, dtype=np.int32))
-    s.finalize()
-    return s
-
-
 def _same_topk(D, I, Dr, Ir):
     """ids equal, except swaps / substitutions between scores closer than the fp32 resolution of the two implementations"""
     np.testing.assert_allclose(D, Dr, rtol=3e-7, atol=1e-5)
