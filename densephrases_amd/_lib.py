@@ -123,6 +123,10 @@ def _load() -> C.CDLL:
         "dph_index_set_pq_list_sizes": (C.c_int, [vp, vp]),
         "dph_index_upload_pq_codes": (C.c_int, [vp, i64, i64, vp, vp]),
         "dph_index_get_transform": (C.c_int, [vp, vp]),
+        "dph_pq_encode_dev": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+        "dph_index_fill_pq_dev": (C.c_int, [vp, i64, vp, vp, vp, vp]),
+        "dph_index_get_pq_list_sizes": (C.c_int, [vp, vp]),
+        "dph_index_download_pq_codes": (C.c_int, [vp, i64, i64, vp, vp]),
         "dph_index_create_twin": (C.c_int, [vp, C.POINTER(vp)]),
         "dph_stream_create_cu_range": (C.c_int, [i32, i32, i32, C.POINTER(vp)]),
         "dph_stream_destroy": (C.c_int, [vp]),
@@ -148,7 +152,8 @@ EXPORTED = ["dph_abi_version", "dph_last_error", "dph_device_count", "dph_index_
             "dph_index_set_tuning", "dph_scan_counters", "dph_debug_wave_pairs", "dph_index_rehome_rows", "dph_index_gather_rows_dev", "dph_kmeans_step_dev", "dph_index_stored_rows", "dph_index_set_id_groups", "dph_ivf_assign_dev", "dph_index_assign_dev", "dph_index_make_list_major", "dph_score_vecs_dev", "dph_score_vecs_bwd_dev", "dph_dense_logits_dev",
             "dph_profile_enable", "dph_profile_read", "dph_profile_read_all", "dph_index_set_row_ids",
             "dph_index_set_ivf", "dph_search_ivf", "dph_search_ivf_dev", "dph_index_create_pq", "dph_index_set_pq",
-            "dph_index_set_pq_list_sizes", "dph_index_upload_pq_codes", "dph_index_get_transform", "dph_index_create_twin",
+            "dph_index_set_pq_list_sizes", "dph_index_upload_pq_codes", "dph_index_get_transform", "dph_pq_encode_dev",
+            "dph_index_fill_pq_dev", "dph_index_get_pq_list_sizes", "dph_index_download_pq_codes", "dph_index_create_twin",
             "dph_stream_create_cu_range", "dph_stream_destroy", "dph_search_prepare_dev", "dph_search_finish_dev"]
 
 
@@ -183,32 +188,15 @@ class Shard:
         set_idx2id / set_id_groups / set_f2o as for a raw-dump shard, then finalize().
         ``keep``: callable ids -> bool mask; only those codes of every list are uploaded -- the shard of ONE rank of a
         range-sharded job (every rank holds the OPQ matrix, all centroids and codebooks, and the codes of its own id range)."""
-        from .faiss_io import IVFPQIndex, PreTransformIndex
-        ivf = index.index if isinstance(index, PreTransformIndex) else index
-        if not isinstance(ivf, IVFPQIndex):
-            raise TypeError("from_faiss_index: an IndexIVFPQ (optionally behind an IndexPreTransform) is needed")
-        A = b = None
-        if isinstance(index, PreTransformIndex):
-            if len(index.chain) != 1 or index.chain[0].A.shape != (DIM, DIM):
-                raise ValueError("from_faiss_index: one 768 x 768 linear pre-transform (the OPQ matrix) is supported")
-            A = np.ascontiguousarray(index.chain[0].A, dtype=np.float32)
-            b = None if index.chain[0].b is None else np.ascontiguousarray(index.chain[0].b, dtype=np.float32)
-        if ivf.d != DIM or ivf.nbits != 8 or ivf.metric != 0:
-            raise ValueError("from_faiss_index: d = 768, 8-bit codes and METRIC_INNER_PRODUCT are supported")
+        ivf = cls._ivf_of(index)
         masks = None
         if keep is not None:
             masks = [np.asarray(keep(np.asarray(i, dtype=np.int64)), dtype=bool) if len(i) else np.zeros(0, bool) for i in ivf.list_ids]
             n_local = int(sum(int(m.sum()) for m in masks))
         else:
             n_local = int(ivf.ntotal)
-        self = cls.__new__(cls)
-        self._h = C.c_void_p()
-        _chk(lib.dph_index_create_pq(int(device), n_local, int(ivf.nlist), int(ivf.M), C.byref(self._h)))
-        self.device, self.id_base, self.n_rows = int(device), 0, n_local
+        self = cls._pq_handle(index, n_local, device)
         try:
-            cent = np.ascontiguousarray(ivf.centroids, dtype=np.float32)
-            pqc = np.ascontiguousarray(ivf.pq_centroids, dtype=np.float32)
-            _chk(lib.dph_index_set_pq(self._h, _p(A), _p(b), _p(cent), _p(pqc), 1 if ivf.by_residual else 0))
             sizes = np.asarray([len(i) for i in ivf.list_ids] if masks is None else [int(m.sum()) for m in masks], dtype=np.int64)
             _chk(lib.dph_index_set_pq_list_sizes(self._h, _p(sizes)))
             pos = 0
@@ -226,8 +214,95 @@ class Shard:
         except Exception:
             self.close()                    # a half-loaded index holds gigabytes of HBM
             raise
+        return self
+
+    @staticmethod
+    def _ivf_of(index):
+        from .faiss_io import IVFPQIndex, PreTransformIndex
+        ivf = index.index if isinstance(index, PreTransformIndex) else index
+        if not isinstance(ivf, IVFPQIndex):
+            raise TypeError("from_faiss_index: an IndexIVFPQ (optionally behind an IndexPreTransform) is needed")
+        return ivf
+
+    @classmethod
+    def _pq_handle(cls, index, ntotal: int, device: int):
+        """A PQ handle for ``ntotal`` codes with the PARAMETERS of a parsed index set -- OPQ matrix, coarse centroids, codebooks -- and no
+        lists yet: what from_faiss_index fills from the file's lists and pq_from_trained leaves to pq_fill_dev."""
+        from .faiss_io import PreTransformIndex
+        ivf = cls._ivf_of(index)
+        A = b = None
+        if isinstance(index, PreTransformIndex):
+            if len(index.chain) != 1 or index.chain[0].A.shape != (DIM, DIM):
+                raise ValueError("from_faiss_index: one 768 x 768 linear pre-transform (the OPQ matrix) is supported")
+            A = np.ascontiguousarray(index.chain[0].A, dtype=np.float32)
+            b = None if index.chain[0].b is None else np.ascontiguousarray(index.chain[0].b, dtype=np.float32)
+        if ivf.d != DIM or ivf.nbits != 8 or ivf.metric != 0:
+            raise ValueError("from_faiss_index: d = 768, 8-bit codes and METRIC_INNER_PRODUCT are supported")
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _chk(lib.dph_index_create_pq(int(device), int(ntotal), int(ivf.nlist), int(ivf.M), C.byref(self._h)))
+        self.device, self.id_base, self.n_rows = int(device), 0, int(ntotal)
+        try:
+            cent = np.ascontiguousarray(ivf.centroids, dtype=np.float32)
+            pqc = np.ascontiguousarray(ivf.pq_centroids, dtype=np.float32)
+            _chk(lib.dph_index_set_pq(self._h, _p(A), _p(b), _p(cent), _p(pqc), 1 if ivf.by_residual else 0))
+        except Exception:
+            self.close()
+            raise
         self.pq = {"nlist": int(ivf.nlist), "M": int(ivf.M), "nprobe": 256}
         return self
+
+    @classmethod
+    def pq_from_trained(cls, index, ntotal: int, device: int = 0):
+        """An EMPTY PQ handle for ``ntotal`` codes behind a parsed TRAINED index (what train_index leaves, build_phrase_index.py:
+        96-142): ready for pq_encode_dev; pq_fill_dev gives it its lists, then set_idx2id / set_f2o / finalize as ever."""
+        return cls._pq_handle(index, ntotal, device)
+
+    def pq_encode_dev(self, x_ptr: int, n: int, list_ptr: int, codes_ptr: int, stream: int = 0):
+        """fp32 rows [n,768] (device) -> list int32 [n], codes uint8 [n,M] (device): dph_pq_encode_dev.  Non-finite row: list -1."""
+        _chk(lib.dph_pq_encode_dev(self._h, C.c_void_p(x_ptr), int(n), C.c_void_p(list_ptr), C.c_void_p(codes_ptr), C.c_void_p(stream)))
+
+    def pq_fill_dev(self, n: int, list_ptr: int, codes_ptr: int, ids_ptr: int, stream: int = 0):
+        """list / codes / ids of ALL ntotal codes (device) -> the handle's inverted lists (dph_index_fill_pq_dev)"""
+        _chk(lib.dph_index_fill_pq_dev(self._h, int(n), C.c_void_p(list_ptr), C.c_void_p(codes_ptr), C.c_void_p(ids_ptr), C.c_void_p(stream)))
+
+    def pq_list_sizes(self) -> np.ndarray:
+        out = np.zeros(self.pq["nlist"], dtype=np.int64)
+        _chk(lib.dph_index_get_pq_list_sizes(self._h, _p(out)))
+        return out
+
+    def pq_download(self, pos0: int, n: int):
+        """(codes uint8 [n,M], ids int64 [n]) of positions [pos0, pos0+n) of the list-major order"""
+        codes = np.empty((int(n), self.pq["M"]), dtype=np.uint8)
+        ids = np.empty(int(n), dtype=np.int64)
+        if n > 0:
+            _chk(lib.dph_index_download_pq_codes(self._h, int(pos0), int(n), _p(codes), _p(ids)))
+        return codes, ids
+
+    def to_faiss_index(self, template, chunk_codes: int = 1 << 22):
+        """The parsed index ``template`` (same parameters as this handle) with this handle's lists filled in: ready for
+        faiss_io.write_index.  The template is not modified."""
+        import copy
+        ivf_t = self._ivf_of(template)
+        if ivf_t.nlist != self.pq["nlist"] or ivf_t.M != self.pq["M"]:
+            raise ValueError("to_faiss_index: the template's nlist / M are not this handle's")
+        sizes = self.pq_list_sizes()
+        n = int(sizes.sum())
+        codes = np.empty((n, self.pq["M"]), dtype=np.uint8)
+        ids = np.empty(n, dtype=np.int64)
+        for o in range(0, n, chunk_codes):
+            m = min(chunk_codes, n - o)
+            codes[o:o + m], ids[o:o + m] = self.pq_download(o, m)
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        ivf = copy.copy(ivf_t)
+        ivf.list_codes = [codes[off[l]:off[l + 1]] for l in range(len(sizes))]
+        ivf.list_ids = [ids[off[l]:off[l + 1]] for l in range(len(sizes))]
+        ivf.ondisk_filename = None
+        if template is ivf_t:
+            return ivf
+        out = copy.copy(template)
+        out.index = ivf
+        return out
 
     def transform(self) -> np.ndarray:
         """A [768,768] of the index's pre-transform x' = A x: what index.py:32 reads as ``self.R`` (identity on raw-dump shards)"""

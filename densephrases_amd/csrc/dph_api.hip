@@ -806,6 +806,29 @@ int dph_index_upload_pq_codes(dph_index* h, int64_t pos0, int64_t n, const uint8
     h->sh->finalized = false;
     return rc;
 }
+// the add step: index.add_with_ids behind a trained index (build_phrase_index.py:145-153; add_to_index :156-279 feeds it the dump)
+int dph_pq_encode_dev(dph_index* h, const float* x_dev, int64_t n, int32_t* list_dev, uint8_t* codes_dev, void* stream) {
+    if (!h || !x_dev || n <= 0 || !list_dev || !codes_dev) return fail(DPH_E_ARG, "dph_pq_encode_dev: bad arguments");
+    if (!h->sh->pq) return fail(DPH_E_STATE, "dph_pq_encode_dev: not a PQ index (dph_index_create_pq)");
+    return dph_pq_encode(h->sh->pq, x_dev, n, list_dev, codes_dev, (hipStream_t)stream);
+}
+int dph_index_fill_pq_dev(dph_index* h, int64_t n, const int32_t* list_dev, const uint8_t* codes_dev, const int64_t* ids_dev, void* stream) {
+    DPH_NOT_TWINNED(h, "dph_index_fill_pq_dev");
+    if (!h || n <= 0 || !list_dev || !codes_dev || !ids_dev) return fail(DPH_E_ARG, "dph_index_fill_pq_dev: bad arguments");
+    if (!h->sh->pq) return fail(DPH_E_STATE, "dph_index_fill_pq_dev: not a PQ index");
+    h->sh->finalized = false;
+    return dph_pq_fill(h->sh->pq, n, list_dev, codes_dev, ids_dev, (hipStream_t)stream);
+}
+int dph_index_get_pq_list_sizes(dph_index* h, int64_t* sizes) {
+    if (!h || !sizes) return fail(DPH_E_ARG, "dph_index_get_pq_list_sizes: bad arguments");
+    if (!h->sh->pq) return fail(DPH_E_STATE, "dph_index_get_pq_list_sizes: not a PQ index");
+    return dph_pq_get_list_sizes(h->sh->pq, sizes);
+}
+int dph_index_download_pq_codes(dph_index* h, int64_t pos0, int64_t n, uint8_t* codes, int64_t* ids) {
+    if (!h || n <= 0 || pos0 < 0 || !codes || !ids) return fail(DPH_E_ARG, "dph_index_download_pq_codes: bad arguments");
+    if (!h->sh->pq) return fail(DPH_E_STATE, "dph_index_download_pq_codes: not a PQ index");
+    return dph_pq_download(h->sh->pq, pos0, n, codes, ids);
+}
 int dph_index_get_transform(dph_index* h, float* A_out) {
     if (!h || !A_out) return fail(DPH_E_ARG, "dph_index_get_transform: null");
     if (h->sh->pq) { memcpy(A_out, dph_pq_A_host(h->sh->pq), (size_t)DPH_DIM * DPH_DIM * 4); return DPH_OK; }
@@ -1849,7 +1872,7 @@ int dph_profile_read(dph_index* h, double* scan_ms_total, int* scan_launches) {
 // every bracketed launch since the last read on its own: which = 0 the full scans (PQ index: the coarse filter scans), 1 the ladder levels'
 int dph_profile_read_each(dph_index* h, int which, double* ms_out, int cap, int* n_out) {
     if (!h || !n_out || cap < 0 || (cap > 0 && !ms_out)) return fail(DPH_E_ARG, "dph_profile_read_each: bad arguments");
-    if (h->sh->pq) return dph_pq_profile_read_each(h->sh->pq, ms_out, cap, n_out);
+    if (h->sh->pq) return dph_pq_profile_read_each(h->sh->pq, which, ms_out, cap, n_out);
     HIPCHK(hipSetDevice(h->device));
     return h->sc.prof.drain(which ? h->sc.prof_events_ladder : h->sc.prof_events, nullptr, n_out, ms_out, cap);
 }

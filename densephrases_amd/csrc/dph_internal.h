@@ -501,6 +501,19 @@ int dph_pq_set_params(dph_pq* p, const float* A, const float* b, const float* ce
 int dph_pq_set_list_sizes(dph_pq* p, const int64_t* sizes);
 int dph_pq_upload(dph_pq* p, int64_t pos0, int64_t n, const uint8_t* codes, const int64_t* ids);
 int dph_pq_finalize(dph_pq* p, hipStream_t st);
+// the add step (build_phrase_index.py:145-153): rows -> (list, codes) behind the handle's parameters, and all codes -> the handle's lists
+int dph_pq_encode(dph_pq* p, const float* x_dev, int64_t n, int32_t* list_dev, uint8_t* codes_dev, hipStream_t st);
+int dph_pq_fill(dph_pq* p, int64_t n, const int32_t* list_dev, const uint8_t* codes_dev, const int64_t* ids_dev, hipStream_t st);
+int dph_pq_get_list_sizes(dph_pq* p, int64_t* sizes);
+int dph_pq_download(dph_pq* p, int64_t pos0, int64_t n, uint8_t* codes, int64_t* ids);
+// ... its kernels (dph_pq_encode.hip)
+void dph_launch_pq_relist(const float* xp, int64_t n, const float* cent, int nlist, const int32_t* nonfinite, const float* gap, double cnorm_max,
+                          int32_t* list, hipStream_t st);
+int dph_launch_pq_codes(const float* xp, int64_t n, const int32_t* list, const float* cent, int by_residual, const float* pqc, const float* bias,
+                        const float* wmax, int M, uint8_t* codes, int device, hipStream_t st);
+void dph_launch_pq_fill_keys(const int32_t* list, int64_t n, int nlist, int64_t* keys, unsigned* vals, unsigned* counts, int* bad, hipStream_t st);
+void dph_launch_pq_fill_gather(const unsigned* src, int64_t n, int M, const uint8_t* codes_in, const int64_t* ids_in, uint8_t* codes_out, int64_t* ids_out,
+                               hipStream_t st);
 bool dph_pq_ready(const dph_pq* p);
 int64_t dph_pq_ntotal(const dph_pq* p);
 int dph_pq_nlist(const dph_pq* p);
@@ -516,7 +529,7 @@ int dph_coarse_select_clock(unsigned long long* out, int cap_rows);
 // measurement hook: HIP events around the coarse quantizer's dominant GEMM launch of every pass (dph_profile_enable / _read on a PQ index)
 int dph_pq_profile(dph_pq* p, int on);
 int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches);
-int dph_pq_profile_read_each(dph_pq* p, double* ms_out, int cap, int* n_out);
+int dph_pq_profile_read_each(dph_pq* p, int which, double* ms_out, int cap, int* n_out);
 int dph_pq_search_dev(dph_pq* p, const float* x_dev, int64_t n, int k, int nprobe, float* D, int64_t* I, int32_t* status, hipStream_t st);
 int dph_pq_reconstruct_dev(dph_pq* p, const int64_t* ids_dev, int64_t n, float* out_dev, int32_t* found_dev, hipStream_t st);
 int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf, int64_t n_q, int k, int L, const int64_t* ids,

@@ -901,6 +901,7 @@ struct dph_pq {
     int device = 0, nlist = 0, M = 0, dsub = 0, by_residual = 1;
     int64_t ntotal = 0;
     dev_buf<float> A, At, b, cent, pqc;
+    dev_buf<float> pqc_bias, pqc_wmax;                     // the encoder's view of the codebooks: fp32(-||w_mj||^2 / 2) [M][256] and max_j ||w_mj|| [M] (rounded up)
     dev_buf<unsigned> cent_pk;                             // bf16 hi << 16 | lo of the centroids (long quantizers: the bf16x3 coarse GEMM)
     dev_buf<unsigned short> cent_hi;                       // the centroids as plain bf16: the coarse quantizer's one-product filter GEMM
     dev_buf<unsigned short> cent_frag;                     // ... once more in MFMA fragment order (filter GEMM variant 3)
@@ -912,6 +913,7 @@ struct dph_pq {
     int coarse_teams = 1;                                  // tuning key "coarse_teams": passes of more than 128 rows run the filter scan as ONE launch of workgroup teams
     dph_profiler prof;
     dph_event_pairs prof_events;                           // around the launches of the coarse filter's dominant kernel
+    dph_event_pairs enc_events;                            // around the four launches of every chunk of dph_pq_encode: transform, assign, re-decide, codes
     std::vector<float> h_A;
     dev_buf<uint8_t> codes; dev_buf<int64_t> ids, list_off;
     std::vector<int64_t> h_list_off;
@@ -926,6 +928,7 @@ struct dph_pq {
     // what lives until the index is freed
     dev_buf<float> qrot; int64_t qrot_rows = 0;            // rotated query halves of dph_pq_window
     dph_coarse_scratch coarse;                             // of the coarse quantizer (dph_launch_coarse / dph_launch_coarse_filter allocate what they need)
+    struct { dev_buf<float> xp, gap; dev_buf<int32_t> nf; int64_t rows = 0; } enc;    // scratch of dph_pq_encode: one chunk of rotated rows, gaps, flags
     dev_buf<unsigned long long> phase_prof;                // dph_debug_pq_phases: [workgroups][8], allocated by the first call
     int phase_wgs = 0;
 };
@@ -1015,10 +1018,10 @@ int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches) {
     HIPCHK(hipSetDevice(p->device));
     return p->prof.drain(p->prof_events, ms_total, launches);
 }
-int dph_pq_profile_read_each(dph_pq* p, double* ms_out, int cap, int* n_out) {
+int dph_pq_profile_read_each(dph_pq* p, int which, double* ms_out, int cap, int* n_out) {
     if (!p || !n_out) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
-    return p->prof.drain(p->prof_events, nullptr, n_out, ms_out, cap);
+    return p->prof.drain(which == 2 ? p->enc_events : p->prof_events, nullptr, n_out, ms_out, cap);
 }
 
 void dph_pq_free(dph_pq* p) {
@@ -1077,6 +1080,26 @@ int dph_pq_set_params(dph_pq* p, const float* A, const float* b, const float* ce
         p->cnorm_cap = std::min(p->cnorm_max, 1.1 * (double)srt[q99]);
         if (!p->cnorm) HIPCHK(p->cnorm.alloc((size_t)p->nlist));
         HIPCHK(hipMemcpy(p->cnorm, cn.data(), (size_t)p->nlist * 4, hipMemcpyHostToDevice));
+    }
+    {
+        // the encoder's bias and bound constant of every codebook: ||w||^2 in float64, sequential in t
+        const int dsub = p->dsub;
+        std::vector<float> bias((size_t)p->M * 256), wmax((size_t)p->M);
+        for (int m = 0; m < p->M; ++m) {
+            double mx2 = 0.0;
+            for (int j = 0; j < 256; ++j) {
+                const float* w = pq_centroids + ((size_t)m * 256 + j) * dsub;
+                double nw = 0.0;
+                for (int t = 0; t < dsub; ++t) nw += (double)w[t] * (double)w[t];
+                bias[(size_t)m * 256 + j] = (float)(-0.5 * nw);
+                mx2 = std::max(mx2, nw);
+            }
+            wmax[(size_t)m] = nextafterf((float)(sqrt(mx2) * (1.0 + 1e-6)), INFINITY);       // (rounded up: it bounds an error)
+        }
+        if (!p->pqc_bias) HIPCHK(p->pqc_bias.alloc(bias.size()));
+        if (!p->pqc_wmax) HIPCHK(p->pqc_wmax.alloc(wmax.size()));
+        HIPCHK(hipMemcpy(p->pqc_bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->pqc_wmax, wmax.data(), wmax.size() * 4, hipMemcpyHostToDevice));
     }
     p->by_residual = by_residual ? 1 : 0;
     p->params_set = true;
@@ -1138,6 +1161,91 @@ int dph_pq_finalize(dph_pq* p, hipStream_t st) {
         if (dup_h) return fail(DPH_E_ARG, "PQ index: duplicate ids in the inverted lists");
     }
     p->finalized = true;
+    return DPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the add step (kernels: dph_pq_encode.hip)
+// x [n,768] fp32 (device) -> list[n], codes[n,M]: a pure function of the parameters, in chunks of PQ_ENC_CHUNK rows through a scratch of
+// one chunk (192 MiB of rotated rows).  A non-finite row comes back with list -1 and zero codes.
+#define PQ_ENC_CHUNK 65536
+int dph_pq_encode(dph_pq* p, const float* x_dev, int64_t n, int32_t* list_dev, uint8_t* codes_dev, hipStream_t st) {
+    if (!p || !x_dev || n <= 0 || !list_dev || !codes_dev) return fail(DPH_E_ARG, "PQ encode: null pointer or no rows");
+    if (((uintptr_t)codes_dev & 15u) || ((uintptr_t)x_dev & 15u)) return fail(DPH_E_ARG, "PQ encode: x and codes must be 16-byte aligned");
+    if (!p->params_set) return fail(DPH_E_STATE, "PQ encode: parameters not set (dph_index_set_pq)");
+    HIPCHK(hipSetDevice(p->device));
+    const int64_t chunk = std::min<int64_t>(n, PQ_ENC_CHUNK);
+    if (p->enc.rows < chunk) {
+        p->enc.rows = 0;
+        HIPCHK(p->enc.xp.alloc((size_t)chunk * DPH_DIM));
+        HIPCHK(p->enc.gap.alloc((size_t)chunk));
+        HIPCHK(p->enc.nf.alloc((size_t)chunk));
+        p->enc.rows = chunk;
+    }
+    dph_event_pairs* ev = p->prof.on ? &p->enc_events : nullptr;
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t m = std::min(chunk, n - r0);
+        const float* x = x_dev + r0 * DPH_DIM;
+        int32_t* list = list_dev + r0;
+        p->prof.bracket(ev, st, [&] { pq_launch_transform(x, p->At, m, p->b, p->enc.xp, nullptr, nullptr, p->device, st, p->enc.nf); });
+        p->prof.bracket(ev, st, [&] { dph_launch_assign(p->enc.xp, false, nullptr, m, p->cent, p->nlist, nullptr, list, p->enc.gap, st); });
+        p->prof.bracket(ev, st, [&] { dph_launch_pq_relist(p->enc.xp, m, p->cent, p->nlist, p->enc.nf, p->enc.gap, p->cnorm_max, list, st); });
+        int rc = 0;
+        p->prof.bracket(ev, st, [&] {
+            rc = dph_launch_pq_codes(p->enc.xp, m, list, p->cent, p->by_residual, p->pqc, p->pqc_bias, p->pqc_wmax, p->M, codes_dev + r0 * p->M, p->device, st);
+        });
+        if (rc) return fail(DPH_E_ARG, "PQ encode: no kernel for this M");
+    }
+    HIPCHK(hipGetLastError());
+    return DPH_OK;
+}
+
+// list[n], codes[n,M], ids[n] of ALL ntotal codes (device) -> the handle's list-major codes / ids / list_off: stable order by (list, input
+// position), FAISS' append order.  A list outside [0, nlist) -- the -1 of a non-finite row -- fails the call before anything is written.
+int dph_pq_fill(dph_pq* p, int64_t n, const int32_t* list_dev, const uint8_t* codes_dev, const int64_t* ids_dev, hipStream_t st) {
+    if (!p || n <= 0 || !list_dev || !codes_dev || !ids_dev) return fail(DPH_E_ARG, "PQ fill: null pointer or no codes");
+    if ((uintptr_t)codes_dev & 15u) return fail(DPH_E_ARG, "PQ fill: codes must be 16-byte aligned");
+    if (!p->params_set) return fail(DPH_E_STATE, "PQ fill: parameters not set (dph_index_set_pq)");
+    if (n != p->ntotal) return fail(DPH_E_ARG, "PQ fill: takes all ntotal codes of the handle at once");
+    HIPCHK(hipSetDevice(p->device));
+    p->finalized = false;
+    dev_buf<int64_t> keys, keys_sorted;
+    dev_buf<unsigned> vals, vals_sorted, counts;
+    dev_buf<int> bad;
+    HIPCHK(keys.alloc((size_t)n)); HIPCHK(keys_sorted.alloc((size_t)n));
+    HIPCHK(vals.alloc((size_t)n)); HIPCHK(vals_sorted.alloc((size_t)n));
+    HIPCHK(counts.alloc((size_t)p->nlist)); HIPCHK(bad.alloc(1));
+    HIPCHK(hipMemsetAsync(counts, 0, (size_t)p->nlist * 4, st));
+    HIPCHK(hipMemsetAsync(bad, 0, 4, st));
+    dph_launch_pq_fill_keys(list_dev, n, p->nlist, keys, vals, counts, bad, st);
+    int bad_h = 0;
+    std::vector<unsigned> cnt((size_t)p->nlist);
+    HIPCHK(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(cnt.data(), counts, (size_t)p->nlist * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad_h) return fail(DPH_E_ARG, "PQ fill: a row's list is outside [0, nlist) (-1 marks a non-finite row)");
+    if (dph_sort_pairs_i64_u32(keys, vals, keys_sorted, vals_sorted, n, st)) return fail(DPH_E_HIP, "PQ fill: sorting by (list, position) failed");
+    dph_launch_pq_fill_gather(vals_sorted, n, p->M, codes_dev, ids_dev, p->codes, p->ids, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int64_t> sizes(cnt.begin(), cnt.end());
+    return dph_pq_set_list_sizes(p, sizes.data());         // list_off, the host copies, the search scratch dropped
+}
+
+int dph_pq_get_list_sizes(dph_pq* p, int64_t* sizes) {
+    if (!p || !sizes) return fail(DPH_E_ARG, "PQ list sizes: null");
+    if (!p->params_set || !p->lists_set) return fail(DPH_E_STATE, "PQ list sizes: parameters / lists not set");
+    for (int l = 0; l < p->nlist; ++l) sizes[l] = p->h_list_off[(size_t)l + 1] - p->h_list_off[(size_t)l];
+    return DPH_OK;
+}
+
+int dph_pq_download(dph_pq* p, int64_t pos0, int64_t n, uint8_t* codes, int64_t* ids) {
+    if (!p || n <= 0 || pos0 < 0 || !codes || !ids) return fail(DPH_E_ARG, "PQ download: null pointer or no codes");
+    if (!p->params_set || !p->lists_set) return fail(DPH_E_STATE, "PQ download: parameters / lists not set");
+    if (pos0 + n > p->ntotal) return fail(DPH_E_ARG, "PQ download: bad code range");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(codes, p->codes + (size_t)pos0 * p->M, (size_t)n * p->M, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ids, p->ids + pos0, (size_t)n * 8, hipMemcpyDeviceToHost));
     return DPH_OK;
 }
 

@@ -79,7 +79,8 @@ def _default_dist():
 class MIPS(object):
     def __init__(self, phrase_dump_dir, index_path, idx2id_path, cuda=False, logging_level=logging.INFO,
                  device: Optional[int] = None, _store=None, rank: Optional[int] = None, world: Optional[int] = None,
-                 dist=None, ivf: Optional[dict] = None, cache_dir: Optional[str] = None, force_collectives: bool = False):
+                 dist=None, ivf: Optional[dict] = None, cache_dir: Optional[str] = None, force_collectives: bool = False,
+                 pq: Optional[dict] = None):
         """Same arguments as the reference (index.py:24).  ``cuda`` is accepted for compatibility; the search always
         runs on the GPU.  ``index_path`` names the reference's ``index.faiss``; no FAISS file is read -- the index
         *is* the int8 dump in idx2id row order (build_phrase_index.py:192-276).
@@ -95,6 +96,12 @@ class MIPS(object):
         (densephrases_amd/ivf.py), then every search -- ``nprobe`` of ``search`` / ``search_dense`` included -- scores
         the rows of the probed lists only.  The permutation happens in HBM (the rows are there twice while it runs);
         ranks of a multi-GPU job must share ``centroids``.
+
+        ``pq={"trained": path or parsed index[, "save": path]}`` compresses the dump behind a TRAINED, empty
+        IndexPreTransform(OPQMatrix) -> IndexIVFPQ (``trained.faiss`` of build_phrase_index.py:96-142): the rows are uploaded as
+        for the flat index, encoded where they lie (densephrases_amd/pq_build.py: the add step of :145-153 on the GPU) and
+        released; from there on the object is what a finished ``index.faiss`` gives.  ``"save"`` also writes that file.
+        Not together with ``ivf=`` or ``world > 1``.
 
         ``cache_dir`` (default: the environment's ``DPH_DUMP_CACHE``, unset = off): the first load of a row range leaves a
         packed copy of its rows and f2o table there (h5.ReferenceDump.attach_row_cache); later starts of the same range
@@ -115,6 +122,8 @@ class MIPS(object):
         self.force_collectives = bool(force_collectives) and self.dist is not None
         if self.world > 1 and self.dist is None:
             raise ValueError("MIPS: world > 1 needs a torch.distributed process group (or a `dist` object)")
+        if pq is not None and (ivf is not None or self.world > 1):
+            raise ValueError("MIPS(pq=...): not together with ivf= (the trained index brings its own lists) or world > 1 (sharded compression is not built)")
         if device is None:
             device = int(os.environ.get("LOCAL_RANK", "0")) if self.world > 1 else 0
         store = _store if _store is not None else load_dump_and_index(phrase_dump_dir, index_path, idx2id_path)
@@ -126,6 +135,8 @@ class MIPS(object):
         from . import faiss_io
         if _store is None and faiss_io.looks_like_faiss_index(str(index_path)):
             parsed = faiss_io.read_index(str(index_path), faiss_io.IO_FLAG_ONDISK_SAME_DIR)        # index.py:30
+            if not isinstance(parsed, faiss_io.FlatIndex) and pq is not None:
+                raise ValueError("MIPS(pq=...) compresses the raw dump; this index file already holds codes")
             if not isinstance(parsed, faiss_io.FlatIndex):
                 # the reference's own index type: OPQ + IVFPQ codes resident in HBM instead of the raw int8 rows
                 self._init_pq(parsed, store, device, ivf)
@@ -134,6 +145,10 @@ class MIPS(object):
             # fine_quant 'none' (build_phrase_index.py:117-118): a flat fp32 index of the de-quantised dump rows -- the
             # resident int8 dump below IS that index
         n = store.n_rows
+        if pq is not None:
+            self._build_pq(store, device, dict(pq))
+            logger.info(f"index ntotal: {self.index.ntotal} | PQ codes built on GPU {device} | load {time() - t0:.1f}s")
+            return
         from .dist import partition_rows
         self.row_lo, self.row_hi = partition_rows(n, self.world, doc_starts=store.doc_starts())[self.rank]
         lo, hi = self.row_lo, self.row_hi
@@ -192,6 +207,41 @@ class MIPS(object):
         self.shard = _lib.Shard.from_faiss_index(parsed, device=device, keep=keep)
         if self.shard.n_rows != hi - lo:
             raise ValueError(f"MIPS: the index holds {self.shard.n_rows} codes for the rows [{lo}, {hi}) of this rank")
+        self._finish_pq(store, lo, hi, n)
+
+    def _build_pq(self, store, device: int, pq: dict):
+        """``pq={"trained": ...}``: the dump's rows go to HBM like a flat shard, add_with_ids_resident turns them into the codes and
+        lists of the trained index (ids = the dump's own: row number, or the id groups of a merged dump), the flat rows are released."""
+        import torch
+        from . import faiss_io
+        from .pq_build import add_with_ids_resident
+        trained = pq["trained"]
+        if isinstance(trained, (str, os.PathLike)):
+            trained = faiss_io.read_index(str(trained))
+        if int(trained.ntotal) != 0:
+            raise ValueError(f"MIPS(pq=...): the trained index must be empty, it holds {trained.ntotal} vectors")
+        n = store.n_rows
+        self.row_lo, self.row_hi = 0, n
+        torch.cuda.set_device(device)
+        flat = self.shard = _lib.Shard(n, device=device, id_base=0)
+        try:
+            flat.set_codec(store.offset, store.scale)
+            self._upload(store, 0, n)
+            ids = None
+            groups = store.id_groups(0, n)
+            if groups is not None:
+                off, rs = np.asarray(groups[0], np.int64), np.asarray(groups[1], np.int64)
+                ids = np.concatenate([off[g] + np.arange(rs[g + 1] - rs[g], dtype=np.int64) for g in range(len(off))])
+            self.shard = add_with_ids_resident(trained, flat, ids=ids, device=device, offset=store.offset, scale=store.scale)
+        finally:
+            flat.close()
+        if pq.get("save"):
+            os.makedirs(os.path.dirname(os.path.abspath(str(pq["save"]))), exist_ok=True)
+            faiss_io.write_index(self.shard.to_faiss_index(trained), str(pq["save"]))
+        self._finish_pq(store, 0, n, n)
+
+    def _finish_pq(self, store, lo: int, hi: int, n: int):
+        """what a PQ shard with its lists in place still needs: the dump's metadata, the direct map, the nprobe clamp, R"""
         self.shard.set_idx2id(store.row2doc[lo:hi], store.row2word[lo:hi])
         groups = store.id_groups(lo, hi)
         if groups is None and self.world > 1:
@@ -296,8 +346,9 @@ class MIPS(object):
             out[:] = store.rows[row0:row0 + out.shape[0]]
 
     @classmethod
-    def from_store(cls, store: DocStore, device: int = 0, logging_level=logging.WARNING, ivf: Optional[dict] = None):
-        return cls(None, "in-memory", None, logging_level=logging_level, device=device, _store=store, ivf=ivf)
+    def from_store(cls, store: DocStore, device: int = 0, logging_level=logging.WARNING, ivf: Optional[dict] = None,
+                   pq: Optional[dict] = None):
+        return cls(None, "in-memory", None, logging_level=logging_level, device=device, _store=store, ivf=ivf, pq=pq)
 
     @classmethod
     def from_shard(cls, shard: "_lib.Shard", store, logging_level=logging.WARNING):

@@ -244,6 +244,27 @@ int dph_index_set_pq(dph_index* h, const float* A, const float* b, const float* 
 int dph_index_set_pq_list_sizes(dph_index* h, const int64_t* sizes);
 int dph_index_upload_pq_codes(dph_index* h, int64_t pos0, int64_t n, const uint8_t* codes, const int64_t* ids);
 int dph_index_get_transform(dph_index* h, float* A_out /* [768*768] */);
+/* ---- filling such an index on the device: index.add_with_ids behind a TRAINED index (build_phrase_index.py:145-153; add_to_index,
+ * :156-279, feeds it the dump rows; training itself -- :96-142 -- is not replaced).  The handle needs its parameters (dph_index_set_pq), no codes.
+ *   dph_pq_encode_dev            replaces the encoding half of add_with_ids (:145-153).  x_dev [n,768] fp32 -> list_dev[n], codes_dev[n,M]:
+ *                                x' = fp32(A x + b) (float64 accumulation, one rounding); list = arg-max_l <x', c_l> in the float64 order, ties to
+ *                                the lowest list (fused MFMA estimate; rows inside the fp32 error band, exact ties included, re-decided in float64
+ *                                over all lists); r = fp32(x' - c_list) with by_residual, else x'; code[m] = arg-min_j ||w_mj||^2 - 2 <r_m, w_mj>
+ *                                as the float64 value with products and sums sequential in t, ties to the lowest j (v_mfma_f32_32x32x2_f32
+ *                                estimate, cells inside the error bound of their dot re-decided in float64 in the same kernel).  A row with a
+ *                                NaN / Inf element gets list -1 and zero codes.  A pure function of the parameters: any chunking, before or after
+ *                                codes exist.  Device pointers, x_dev and codes_dev 16-byte aligned; asynchronous on `stream`.
+ *   dph_index_fill_pq_dev        replaces the inverted-list half of add_with_ids (:145-153, ids = arange + offset + start_total at :149): list_dev[n],
+ *                                codes_dev[n,M], ids_dev[n] of ALL n == ntotal codes (device) become the handle's lists, codes of one list in input
+ *                                order (FAISS' append order).  A list outside [0, nlist) -- the -1 of a non-finite row -- fails with DPH_E_ARG and the
+ *                                handle stays unfinalized.  Synchronous.  Then set_idx2id / set_f2o / dph_index_finalize as ever.
+ *   dph_index_get_pq_list_sizes  sizes[nlist] of the lists (what faiss invlists.list_size(l) answers; merge_indexes reads them, :282-338)
+ *   dph_index_download_pq_codes  codes [n,M] and ids [n] of positions [pos0, pos0+n) back to HOST memory: what faiss.write_index needs of the
+ *                                lists (add_to_index ends with it, :156-279) */
+int dph_pq_encode_dev(dph_index* h, const float* x_dev, int64_t n, int32_t* list_dev, uint8_t* codes_dev /*[n,M]*/, void* stream);
+int dph_index_fill_pq_dev(dph_index* h, int64_t n /* == ntotal */, const int32_t* list_dev, const uint8_t* codes_dev, const int64_t* ids_dev, void* stream);
+int dph_index_get_pq_list_sizes(dph_index* h, int64_t* sizes /*[nlist]*/);
+int dph_index_download_pq_codes(dph_index* h, int64_t pos0, int64_t n, uint8_t* codes, int64_t* ids);
 
 /* ---- faiss reconstruct (index.py:31, 286, 296) ---- de-quantised fp32 row of a global id */
 int dph_reconstruct(dph_index* h, int64_t id, float* out768);
