@@ -70,7 +70,7 @@ __global__ __launch_bounds__(SEL_THREADS) void dph_select_kernel(
     const bool lost = raw > (unsigned)DPH_BUCKET_CAP || overflow[qi] != 0u;
     if (only_failed && lost) return;            // a wider re-score cannot repair lost pairs: the row stays flagged for the re-scan
     const uint64_t* keys = buckets + (int64_t)qi * DPH_BUCKET_CAP;
-    if (tid == 0) { red[8] = 0; red[10] = (int)0x80000000; red[12] = 0; red[13] = 0; }
+    if (tid == 0) { red[8] = 0; red[9] = -1; red[10] = (int)0x80000000; red[12] = 0; red[13] = 0; }
     // More keys than the sort holds (8192), all of them in the bucket (round 4; rounds 1-3 called that "lost" and re-scanned the whole
     // shard for the row -- one bench batch in four on the document-ordered dump, whose buckets run 2.4 k keys in the median and up to
     // 8.4 k): take the DPH_POOL_MAX best by integer score.  Radix select of the threshold score sT (4 x 8 bits over the bucket in
@@ -194,6 +194,7 @@ __global__ __launch_bounds__(SEL_THREADS) void dph_select_kernel(
             I[orow * k + rank] = r;
         }
         if (rank == k - 1) red[8] = c;          // exactly one candidate has this rank
+        if (rank == k) red[9] = c;              // ... and this one: the best candidate that is NOT returned
     }
     for (int c = nc + tid; c < k; c += SEL_THREADS) {   // FAISS padding
         D[orow * k + c] = -FLT_MAX_F;
@@ -234,7 +235,11 @@ __global__ __launch_bounds__(SEL_THREADS) void dph_select_kernel(
         // sharded search under a bound taken over all shards: this shard may hold fewer than k rows above it, and
         // its k-th may be beaten elsewhere -- the merge decides (certified iff the merged k-th beats `bound`)
         if (bound_out && st == 1 && !lost) st = 2;
-        if (bound_out) bound_out[orow] = bound;
+        // what the caller is told covers EVERY row that was not returned (dph.h): a certified row also left re-scored candidates
+        // behind (they lost to its k-th in (S desc, id asc) order -- `bound` says nothing about them and may well lie below them), so
+        // the best of those joins the bound that is handed out.  An uncertified row's k-th is <= bound already, and so are they.
+        // (The merge reads the bound of status-2 rows only: no decision depends on this.)
+        if (bound_out) bound_out[orow] = (st == 0 && red[9] >= 0) ? fmax(bound, cS[red[9]]) : bound;
         status[orow] = st;
         if (only_failed && st == 0 && reselect_count) atomicAdd(reselect_count, 1);
     }

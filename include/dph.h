@@ -320,7 +320,13 @@ int dph_dense_logits_dev(int device, const float* start_logits_dev, const float*
  * all-gather of those [n,16] arrays dph_union_bounds_dev takes the 16-th best of the union, minus one -- a lower bound
  * of the 16-th best row of the whole dump.  Phase 2 scans under these bounds; a shard may then hold fewer than k rows
  * above the bound, so besides D/I (padded with -1) it returns bound_dev[r] = an upper bound of the reference score of
- * every row it did NOT return, and status 0 (own top-k closed) or 2 (decided by dph_merge_records_dev). */
+ * every row it did NOT return, and status 0 (own top-k closed) or 2 (decided by dph_merge_records_dev).
+ * The rule behind bound_dev (csrc/dph_select.hip, tests/_certificate_ref.py restates it): a row that was not RE-SCORED has
+ *   S <= (sc a_rest + ||e||_2 rmax + <e, mu>) / scale + offset sum(q) + ||q||_1 dmax,   a_rest = max(tau, best key left, radix cut),
+ * with rmax_all for outlier rows; status 0 <=> the k-th returned score beats that.  A row of status 0 also re-scored
+ * candidates it did not return -- they lost to its k-th in (score desc, id asc) order and may lie above the rule's value --
+ * so bound_dev of a status-0 row is the larger of the rule's value and the best of those.  With status 2 the k-th
+ * returned score is <= the rule's value and so is every such candidate: bound_dev is the rule's value itself. */
 int dph_search_sample_dev(dph_index* h, const float* x_dev, int64_t n, int32_t* top_dev /* [n,16] */, void* stream);
 int dph_union_bounds_dev(int device, const int32_t* top_parts /* [n_parts,n,16] */, int n_parts, int64_t n,
                          int32_t* tau_dev /* [n] */, void* stream);
