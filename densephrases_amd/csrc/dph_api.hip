@@ -870,16 +870,12 @@ int dph_index_set_tuning(dph_index* h, const char* key, const int32_t* values, i
         dph_pq_set_coarse_teams(h->sh->pq, values[0]);
         return DPH_OK;
     }
-    if (k == "coarse_filter") {          // PQ index: 1 = the one-product filter GEMM in front of the coarse quantizer (default), 0 = the bf16x3 chain alone
+    if (k == "coarse_filter") {          // PQ index: 1 = the one-product filter scan in front of the coarse quantizer's chain (default), 0 = the bf16x3 chain alone
         if (!h->sh->pq) return fail(DPH_E_STATE, "coarse_filter: not a PQ index");
-        if (n_values != 1 || values[0] < 0 || values[0] > 5) return fail(DPH_E_ARG, "coarse_filter: 0 .. 5");
+        // (5: how the filter scan was selected while the GEMM forms 1 .. 4 existed; a request for one of those fails rather than be served by the scan)
+        if (n_values != 1 || (values[0] != 0 && values[0] != 1 && values[0] != 5))
+            return fail(DPH_E_ARG, "coarse_filter: 0 (the chain alone), 1 (the filter scan in front of it) or 5 (the old spelling of 1)");
         dph_pq_set_coarse_filter(h->sh->pq, values[0]);
-        return DPH_OK;
-    }
-    if (k == "pq_split_lut") {           // PQ index, row-major ADC scan: 1 = the last sixteen tables are gathered from global memory (vector L1), the rest from LDS
-        if (!h->sh->pq) return fail(DPH_E_STATE, "pq_split_lut: not a PQ index");
-        if (n_values != 1 || values[0] < 0 || values[0] > 1) return fail(DPH_E_ARG, "pq_split_lut: 0 or 1");
-        dph_pq_set_split_lut(h->sh->pq, values[0]);
         return DPH_OK;
     }
     if (k == "retry_chain") return one(0, 1, &h->tune.retry_chain);
@@ -1972,15 +1968,6 @@ int dph_debug_pq_pass(dph_index* h, int32_t info[8], uint32_t* per_row, int n_ro
     if (!h || !info || n_rows < 0 || (n_rows > 0 && !per_row)) return fail(DPH_E_ARG, "dph_debug_pq_pass: bad arguments");
     if (!h->sh->pq) return fail(DPH_E_STATE, "dph_debug_pq_pass: not a PQ index");
     return dph_pq_debug_pass(h->sh->pq, info, per_row, n_rows);
-}
-
-int dph_debug_pq_pool(dph_index* h, uint32_t* lk_host, uint16_t* q_host, int64_t cap, int64_t* count) {
-    if (!h || !lk_host || !q_host || !count || cap < 0) return fail(DPH_E_ARG, "null");
-    if (!h->sh->pq) return fail(DPH_E_STATE, "dph_debug_pq_pool: not a PQ index");
-    long long c = 0;
-    const int rc = dph_pq_coarse_debug_pool(h->sh->pq, lk_host, q_host, cap, &c);
-    *count = c;
-    return rc;
 }
 
 int dph_debug_pq_phases(dph_index* h, int which, uint64_t* out, int cap_wgs, int* n_wgs) {

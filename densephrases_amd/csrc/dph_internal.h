@@ -351,21 +351,19 @@ void dph_launch_select(const dph_pass& p, const dph_select_args& a, hipStream_t 
 struct dph_coarse_counters {            // cleared by one memset per filter pass
     unsigned cand_cnt[DPH_PASS_MAX];    // candidates of every row
     unsigned est[DPH_PASS_MAX];         // threshold estimate (score key) of every row
-    unsigned pool_count, fail;          // triples in the linear pool; 1 = the pass fails over to the chain
+    unsigned pool_count, fail;          // pairs the scan emitted (a statistic); 1 = the pass fails over to the chain
     int gate;                           // rows the fail-over chain serves: all of the pass or none
-    unsigned sink;                      // takes the pool statistic when DPH_CF_KEEP_POOL fills pool_count itself
-    unsigned spare[12];
+    unsigned spare[13];                 // (pads the struct to a whole number of 16-byte units)
 };
 struct dph_coarse_scratch {
     struct chain_part {                 // one-pass probe selection over long score rows
         dev_buf<uint2> cand; dev_buf<unsigned> cand_cnt, est;      // [DPH_PASS_MAX][CS_CAND] (list, key), [DPH_PASS_MAX], [DPH_PASS_MAX]
     } chain;
-    struct filter_part {                // the filter form; its candidate lists are its own (the fail-over chain runs behind it)
+    struct filter_part {                // the filter; its candidate lists are its own (the fail-over chain runs behind it)
         dev_buf<float> sample;                                      // [DPH_PASS_MAX][CF_SAMPLE] scores of the sampled lists
-        dev_buf<uint2> pool_lk; dev_buf<unsigned short> pool_q;     // linear pool: (list, key) and query row of up to CS_CAND triples per row
         dev_buf<uint2> cand;                                        // [DPH_PASS_MAX][CS_CAND]
         dev_buf<dph_coarse_counters> cnt;                           // [1]
-        // the scan form (variant 5): pair pool and its chunk fills, per-wave statistics, queue counters, query fragments of a whole pass
+        // the filter scan: pair pool and its chunk fills, per-wave statistics, queue counters, query fragments of a whole pass
         dev_buf<uint2> pairs; dev_buf<unsigned> chunk_fill, wave_counts; dev_buf<int> counters; dev_buf<uint4> qfrag;
     } filter;
 };
@@ -395,38 +393,32 @@ void dph_launch_coarse(const dph_coarse_args& a, dph_coarse_scratch& s, hipStrea
 #define DPH_SCAN_X16 1
 #endif
 __host__ __device__ static inline bool dph_frag_x16(int aux_stride) { (void)aux_stride; return DPH_SCAN_X16 != 0; }
-// long quantizers, the filter form: one-product bf16 GEMM with the threshold test in its epilogue (dph_ivf.hip).  A whole pass from row 0
-// (q0 = 0, no gate, no tiles); c_pk / x_pk feed its fail-over chain.
+// long quantizers, the filter in front of the chain: a one-product bf16 scan under a sampled threshold (dph_ivf.hip).  A whole pass from
+// row 0 (q0 = 0, no gate, no tiles); c_pk / x_pk feed its fail-over chain.
 struct dph_coarse_filter_args : dph_coarse_args {
-    const unsigned short* c_hi = nullptr; const unsigned short* x_hi = nullptr;       // bf16 images of the centroids (tiled) and of the query rows
-    int variant = 1;                    // 2: the centroid stream loaded non-temporal, 3: centroids straight into registers from c_frag,
-                                        // 5: the filter scan over c_pieces
-    const unsigned short* c_frag = nullptr; const unsigned short* c_pieces = nullptr;
+    const unsigned short* c_hi = nullptr; const unsigned short* x_hi = nullptr;       // bf16 images of the centroids (chunk-major) and of the query rows
+    const unsigned short* c_pieces = nullptr;                                         // the centroids piece-major (NULL: the chain alone)
     const float* cnorm = nullptr;       // [nlist] ||c_l||_2 (device)
     double cnorm_cap = 0.0;             // lists longer than this get exact scores
-    int teams = 1;                      // variant 5, more than 128 rows: one launch of workgroup teams sharing tiles through L2 (dph_scan.hip MODE 4)
-    // profiling: an event pair of its own around EVERY launch of the filter's dominant kernel (the scan; the GEMM forms: the one GEMM
-    // launch), appended to prof_list.  Both NULL: none
+    int teams = 1;                      // more than 128 rows: one launch of workgroup teams sharing tiles through L2 (dph_scan.hip MODE 4)
+    // profiling: an event pair of its own around EVERY launch of the filter's dominant kernel (the scan), appended to prof_list.
+    // Both NULL: none
     dph_profiler* prof = nullptr; dph_event_pairs* prof_list = nullptr;
 };
 void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratch& s, hipStream_t st);
 void dph_launch_coarse_scan_teams(const void* img, int64_t n_lists, const void* qfrag, int n_q, int n_groups, const unsigned* est_keys, uint2* pairs,
                                   unsigned* chunk_fill, unsigned* wave_counts, int* counters, int grid, hipStream_t st);
-// variant 5: the coarse quantizer as a filter SCAN (dph_scan.hip MODE 3) over the piece-major bf16 image
+// the coarse quantizer's filter as a SCAN (dph_scan.hip MODE 3) over the piece-major bf16 image
 // [tile of 32 lists][half of k][32 rows][384 bf16] (dph_launch_bf16_pieces; dph_bf16_piece_rows(n) rows allocated); hits land in
 // chunks of the pair pool as (list | query row << 20, score key)
 void dph_launch_bf16_pieces(const float* v, int64_t n_rows, unsigned short* out, hipStream_t st);
 int64_t dph_bf16_piece_rows(int64_t n_rows);
 void dph_launch_coarse_scan(const void* img, int64_t n_lists, const void* qfrag, int n_q, const unsigned* est_keys, uint2* pairs,
                             unsigned* chunk_fill, unsigned* wave_counts, int* counters, int grid, hipStream_t st);
-// the fragment-major bf16 image variant 3 streams (dph_bf16_frag_rows(n) rows allocated)
-void dph_launch_bf16_frag(const float* v, int64_t n_rows, unsigned short* out, hipStream_t st);
-int64_t dph_bf16_frag_rows(int64_t n_rows);
 int dph_coarse_filter_debug(const dph_coarse_scratch& s, unsigned out[2]);
-long long dph_coarse_filter_debug_pool(const dph_coarse_scratch& s, unsigned* lk_host, unsigned short* q_host, long long cap);
-// bf16 image of a [n_rows, 768] fp32 matrix; tiled = 1: the tile-major layout the filter GEMM streams (dph_bf16_hi_rows(n, 1) rows allocated)
-void dph_launch_bf16_hi(const float* v, int64_t n_rows, int tiled, unsigned short* hi, hipStream_t st);
-int64_t dph_bf16_hi_rows(int64_t n_rows, int tiled);
+// chunk-major bf16 image of a [n_rows, 768] fp32 matrix, what the sample GEMM reads (dph_bf16_hi_rows(n) rows allocated)
+void dph_launch_bf16_hi(const float* v, int64_t n_rows, unsigned short* hi, hipStream_t st);
+int64_t dph_bf16_hi_rows(int64_t n_rows);
 void dph_launch_bf16_split(const float* v, int64_t n_elems, unsigned* packed, hipStream_t st);
 // IVF scratch of a handle: what a pass writes (dph_index_set_ivf sizes it from the lists) ...
 struct dph_ivf_pass {
@@ -520,13 +512,11 @@ int dph_pq_nlist(const dph_pq* p);
 const float* dph_pq_A_host(const dph_pq* p);
 void dph_pq_set_coarse_teams(dph_pq* p, int on);               // tuning key "coarse_teams"
 void dph_pq_set_coarse_filter(dph_pq* p, int on);              // tuning key "coarse_filter"
-void dph_pq_set_split_lut(dph_pq* p, int on);                  // tuning key "pq_split_lut"
 int dph_pq_coarse_debug(dph_pq* p, unsigned out[2]);
-int dph_pq_coarse_debug_pool(dph_pq* p, unsigned* lk_host, unsigned short* q_host, long long cap, long long* count);
 int dph_pq_debug_phases(dph_pq* p, int which, unsigned long long* out, int cap);
 int dph_pq_debug_pass(dph_pq* p, int* info, unsigned* per_row, int n);
 int dph_coarse_select_clock(unsigned long long* out, int cap_rows);
-// measurement hook: HIP events around the coarse quantizer's dominant GEMM launch of every pass (dph_profile_enable / _read on a PQ index)
+// measurement hook: HIP events around the launches of the coarse quantizer's dominant kernel, the filter scan, in every pass (dph_profile_enable / _read on a PQ index)
 int dph_pq_profile(dph_pq* p, int on);
 int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches);
 int dph_pq_profile_read_each(dph_pq* p, int which, double* ms_out, int cap, int* n_out);

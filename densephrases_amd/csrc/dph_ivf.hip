@@ -356,80 +356,71 @@ __device__ __forceinline__ unsigned cs_select_kth(F key_at, int n, int want, uns
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Long quantizers, the filter form (round 4).  The bf16x3 GEMM above reads 4 bytes per centroid component and writes a
+// Long quantizers, the filter in front of the chain.  The bf16x3 GEMM above reads 4 bytes per centroid component and writes a
 // [rows, nlist] score matrix that two more passes read back (estimate + collect): at 2^20 lists that is 3.2 GB + 2 x 0.5 GB
 // per batch of 64.  The probe set only needs the scores NEAR the nprobe-th one exactly, so the first pass is a FILTER:
 //   * the centroids once more as plain bf16 (the hi parts: 2 bytes per component, 1.6 GB at 2^20 lists), the rotated queries
 //     likewise; <x~, c~> with ONE v_mfma_f32_32x32x16_bf16 per tile step.  |<x~,c~> - <x,c>| <= (2^-8 + 2^-18) sum|x_j c_j|
 //     (two roundings to 8 significant bits) + the fp32 accumulation <= CF_HI_ERR * ||x|| * ||c||;
-//   * a threshold estimate per query row from the scores of every (nlist/8192)-th list (the same kernel over a strided sample:
-//     12.6 MB), an order statistic chosen so that ~4-5 x nprobe lists beat it;
-//   * the threshold test sits in the GEMM's epilogue: a (row, list, key) triple per score at or above the row's estimate goes
-//     to a pool (LDS-aggregated, one global atomic per workgroup tile) -- the score matrix is never written;
-//   * dph_coarse_bucket_kernel deals the pool into per-row candidate lists, dph_coarse_select_kernel selects the nprobe-th
-//     candidate, marks what is clearly above the error band and re-ranks the band in float64 exactly as before -- the band is
-//     wider (the 2^-8 error: a few hundred lists around the 256-th of 2^20), which is what the float64 re-rank is for.
+//   * a threshold estimate per query row from the scores of every (nlist/8192)-th list (dph_coarse_sample_gemm_kernel reads
+//     12.6 MB of the chunk-major image, dph_coarse_estimate_sample_kernel takes the order statistic), chosen so that
+//     ~4-5 x nprobe lists beat it;
+//   * the filter itself is a SCAN of the piece-major image (dph_scan.hip MODE 3, MODE 4 for teams): every score at or above its
+//     row's estimate leaves as a (list | query row << 20, key) pair in a chunk of the pair pool -- the score matrix is never
+//     written;
+//   * dph_coarse_bucket_chunks_kernel deals the chunks into per-row candidate lists, dph_coarse_select_kernel selects the
+//     nprobe-th candidate, marks what is clearly above the error band and re-ranks the band in float64 exactly as before -- the
+//     band is wider (the 2^-8 error: a few hundred lists around the 256-th of 2^20), which is what the float64 re-rank is for.
 // A row whose estimate was too high (fewer than nprobe candidates, or the band reaching below it), whose candidates or band
 // overflow, fails the whole pass over to the bf16x3 chain (gated on the device: no host round trip; empty launches otherwise).
-#define CF_K 128                     // k-chunk of the filter GEMM = one run of the tile-major centroid image
+// (Rounds 4-5 also had four GEMM forms of the filter, the threshold test in their epilogue: measured and removed, DESIGN_HISTORY.md.)
+#define CF_K 128                     // k-chunk of the sample GEMM = one run of the chunk-major centroid image
 #define CF_HI_ERR (1.0 / 256.0 + 1.0 / 262144.0 + 800.0 * 5.97e-8)
-#define CF_HIT_CAP 4096              // (row, list, key) triples one workgroup tile can hold before the pass fails over
 #define CF_SAMPLE 8192               // lists of the threshold sample
 
-// The bf16 image of a [n, 768] fp32 matrix the filter GEMM reads.  tiled = 0: row-major (the query rows of a pass).  tiled = 1 (the
-// centroids): CHUNK-MAJOR -- [k-chunk of 128][tile of 128 rows][row][k]: the 32 KiB a workgroup stages per step are one contiguous run,
-// and the runs the workgroups of a launch read in the same step (tiles w, w+1, ... of one k-chunk) follow each other -- hundreds of
-// workgroups sweep one 16 MiB window together.  Row-major, a step gathered 128 pieces of 256 B at a stride of 1536 B (4.1 TB/s whatever
-// was in flight); tile-major ([tile][k-chunk]...: runs 192 KiB apart, every workgroup on the same few memory channels at the same
-// moment) was three times slower than that.  Rows past n in the last tile are written as zeros (the allocation holds whole tiles).
+// The bf16 image of the centroids [n, 768] the sample GEMM reads (the query rows of a pass are plain row-major bf16).
+// CHUNK-MAJOR -- [k-chunk of 128][tile of 128 rows][row][k]: the 32 KiB of a tile and k-chunk are one contiguous run, and the runs of
+// the tiles w, w+1, ... of one k-chunk follow each other.  (The layout was chosen for the GEMM form of the filter, which streamed all
+// of it: row-major, a step gathered 128 pieces of 256 B at a stride of 1536 B; tile-major, [tile][k-chunk]..., was three times slower
+// than that.)  Rows past n in the last tile are written as zeros (the allocation holds whole tiles).
 __host__ __device__ inline int64_t dph_cf_tiled_index(int64_t row, int k, int64_t n_tiles) {
     return ((int64_t)(k / CF_K) * n_tiles + row / CG_LISTS) * (int64_t)(CG_LISTS * CF_K) + (row % CG_LISTS) * CF_K + k % CF_K;
 }
-__global__ __launch_bounds__(256) void dph_bf16_hi_kernel(const float* __restrict__ v, int64_t n_rows, int64_t n_rows_padded, int tiled,
+__global__ __launch_bounds__(256) void dph_bf16_hi_kernel(const float* __restrict__ v, int64_t n_rows, int64_t n_rows_padded,
                                                           unsigned short* __restrict__ hi) {
     const int64_t n_elems = n_rows_padded * DPH_DIM;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_elems; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / DPH_DIM;
         const int k = (int)(i % DPH_DIM);
-        const unsigned short h = row < n_rows ? bf16_rne(v[i]) : (unsigned short)0;
-        hi[tiled ? dph_cf_tiled_index(row, k, n_rows_padded / CG_LISTS) : i] = h;
+        hi[dph_cf_tiled_index(row, k, n_rows_padded / CG_LISTS)] = row < n_rows ? bf16_rne(v[i]) : (unsigned short)0;
     }
 }
-int64_t dph_bf16_hi_rows(int64_t n_rows, int tiled) { return tiled ? (n_rows + CG_LISTS - 1) / CG_LISTS * CG_LISTS : n_rows; }
-void dph_launch_bf16_hi(const float* v, int64_t n_rows, int tiled, unsigned short* hi, hipStream_t st) {
-    const int64_t n_elems = dph_bf16_hi_rows(n_rows, tiled) * DPH_DIM;
+int64_t dph_bf16_hi_rows(int64_t n_rows) { return (n_rows + CG_LISTS - 1) / CG_LISTS * CG_LISTS; }
+void dph_launch_bf16_hi(const float* v, int64_t n_rows, unsigned short* hi, hipStream_t st) {
+    const int64_t n_elems = dph_bf16_hi_rows(n_rows) * DPH_DIM;
     if (n_elems > 0)
         hipLaunchKernelGGL(dph_bf16_hi_kernel, dim3((unsigned)std::min<int64_t>((n_elems + 255) / 256, 1 << 16)), dim3(256), 0, st, v, n_rows,
-                           dph_bf16_hi_rows(n_rows, tiled), tiled, hi);
+                           dph_bf16_hi_rows(n_rows), hi);
 }
 
-// SAMPLE: lists i * list_stride, i < n_lists, scores written to sample_scores[q][i].  Otherwise: all n_lists lists, hits to the pool.
-// Persistent workgroups (two per CU: grid.x = 2 x CUs, or fewer tiles): workgroup w multiplies the list tiles w, w + grid.x, ... as ONE
-// stream of k-chunks of 128 -- the centroid chunk two steps ahead and the query chunk one step ahead are in flight in registers while
-// the current chunk is multiplied out of LDS, across tile boundaries (the epilogue of a tile runs under the next tile's loads).  One
-// chunk ahead kept 64 KiB per CU in flight: 4.1 TB/s at the ~4 us the loads take under load; two chunks ahead doubles that.
+// The sample GEMM: sample_scores[q][i] = <x~_q, c~_l> for the lists l = i * list_stride, i < n_lists.
+// Persistent workgroups (two per CU: grid.x = 2 x CUs, or fewer tiles): workgroup w multiplies the tiles of 128 sampled lists w,
+// w + grid.x, ... as ONE stream of k-chunks of 128 -- the centroid chunk two steps ahead and the query chunk one step ahead are in
+// flight in registers while the current chunk is multiplied out of LDS, across tile boundaries (the epilogue of a tile runs under the
+// next tile's loads).
 typedef unsigned cf_v4u __attribute__((ext_vector_type(4)));
-// every byte of the centroid image is read once per launch by one workgroup: tuning key "coarse_nt" = 1 marks those loads non-temporal
-#define CF_STREAM_LOAD(p) (NT ? __builtin_nontemporal_load(p) : *(p))
-template <bool SAMPLE, bool NT = false>
-__global__ __launch_bounds__(256, 2) void dph_coarse_filter_gemm_kernel(int n_q, int n_lists, int list_stride, int64_t image_tiles,
+__global__ __launch_bounds__(256, 2) void dph_coarse_sample_gemm_kernel(int n_q, int n_lists, int list_stride, int64_t image_tiles,
                                                                         const unsigned short* __restrict__ c_hi,
                                                                         const unsigned short* __restrict__ x_hi,
-                                                                        float* __restrict__ sample_scores, const unsigned* __restrict__ est,
-                                                                        uint2* __restrict__ pool_lk, unsigned short* __restrict__ pool_q,
-                                                                        unsigned* __restrict__ pool_count, unsigned pool_cap,
-                                                                        unsigned* __restrict__ fail) {
+                                                                        float* __restrict__ sample_scores) {
     constexpr int CK = CF_K;
     constexpr int LD = CK + 8;                                    // bf16 per LDS row (CK + 8 of padding: 16-byte aligned rows, conflict-free ds_read_b128)
     constexpr int NF = CK / 16;                                   // uint4 per thread and operand per chunk (256 threads, 128 rows of CK bf16)
     constexpr int CPR = CK / 8;                                   // uint4 per row
     constexpr int NCH = DPH_DIM / CK;                             // chunks per tile
-    constexpr unsigned HIT_CAP = (unsigned)CF_HIT_CAP;            // (row, list, key) triples the staging area holds afterwards (10 bytes each)
-    extern __shared__ __attribute__((aligned(16))) unsigned short cf_lds[];       // a | b, each [128][LD]; afterwards the hit list
+    extern __shared__ __attribute__((aligned(16))) unsigned short cf_lds[];       // a | b, each [128][LD]
     unsigned short* const a_s = cf_lds;
     unsigned short* const b_s = a_s + CG_LISTS * LD;
-    __shared__ unsigned hit_n;
-    __shared__ unsigned hit_base;
     const int qb0 = blockIdx.y * CG_QROWS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = tid % CPR, row0 = tid / CPR;                  // rows row0 + (256 / CPR) i
@@ -450,17 +441,11 @@ __global__ __launch_bounds__(256, 2) void dph_coarse_filter_gemm_kernel(int n_q,
     do {                                                                                                                         \
         const int c_ = (C);                                                                                                      \
         const int l0_ = ((int)blockIdx.x + (c_ / NCH) * (int)gridDim.x) * CG_LISTS, k0_ = (c_ % NCH) * CK;                        \
-        if constexpr (SAMPLE) {                                                                                                  \
-            /* the sample's lists are every list_stride-th list of the index: 256-byte pieces of the chunk-major image */        \
-            _Pragma("unroll") for (int i = 0; i < NF; ++i) {                                                                     \
-                const int l = l0_ + row0 + RSTEP * i;                                                                            \
-                RA[i] = l < n_lists ? *(const cf_v4u*)(c_hi + dph_cf_tiled_index((int64_t)l * list_stride, k0_ + 8 * col, image_tiles)) \
-                                    : cf_v4u{0u, 0u, 0u, 0u};                                                                \
-            }                                                                                                                    \
-        } else {                                                                                                                 \
-            /* chunk (k0 / CK, tile) of the chunk-major image: 32 KiB in one run (rows past n_lists in the last tile are zeros) */ \
-            const cf_v4u* src_ = (const cf_v4u*)(c_hi + ((int64_t)(c_ % NCH) * image_tiles + l0_ / CG_LISTS) * (int64_t)(CG_LISTS * CK)); \
-            _Pragma("unroll") for (int i = 0; i < NF; ++i) RA[i] = CF_STREAM_LOAD(src_ + (row0 + RSTEP * i) * CPR + col);           \
+        /* the sample's lists are every list_stride-th list of the index: 256-byte pieces of the chunk-major image */            \
+        _Pragma("unroll") for (int i = 0; i < NF; ++i) {                                                                         \
+            const int l = l0_ + row0 + RSTEP * i;                                                                                \
+            RA[i] = l < n_lists ? *(const cf_v4u*)(c_hi + dph_cf_tiled_index((int64_t)l * list_stride, k0_ + 8 * col, image_tiles))\
+                                : cf_v4u{0u, 0u, 0u, 0u};                                                                        \
         }                                                                                                                        \
     } while (0)
     auto fetch_b = [&](int c) __attribute__((always_inline)) {
@@ -474,57 +459,15 @@ __global__ __launch_bounds__(256, 2) void dph_coarse_filter_gemm_kernel(int n_q,
     // (always_inline: as an out-of-line call the lambda takes the accumulators by reference, i.e. through scratch memory -- 3x the kernel time)
     auto epilogue = [&](int tile) __attribute__((always_inline)) {
         const int l0 = tile * CG_LISTS;
-        if constexpr (SAMPLE) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int q = qb0 + j * 32 + (lane & 31);
-                if (q >= n_q) continue;
+        for (int j = 0; j < 4; ++j) {
+            const int q = qb0 + j * 32 + (lane & 31);
+            if (q >= n_q) continue;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int l = l0 + wave * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                    if (l < n_lists) sample_scores[(int64_t)q * n_lists + l] = acc[j][r];
-                }
+            for (int r = 0; r < 16; ++r) {
+                const int l = l0 + wave * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+                if (l < n_lists) sample_scores[(int64_t)q * n_lists + l] = acc[j][r];
             }
-        } else {
-            // every score at or above its row's estimate becomes a (row, list, key) triple; the tile's triples are gathered in LDS
-            // (the staging area is free: the chunk loop ended on a barrier) and leave with ONE global atomic
-            uint2* const hit_lk = (uint2*)cf_lds;                     // [HIT_CAP]
-            unsigned short* const hit_q = (unsigned short*)(hit_lk + HIT_CAP);
-            if (tid == 0) hit_n = 0;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int q = qb0 + j * 32 + (lane & 31);
-                const unsigned e = q < n_q ? est[q] : 0xFFFFFFFFu;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int l = l0 + wave * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                    const unsigned key = f32_key(acc[j][r]);
-                    const bool hit = q < n_q && l < n_lists && key >= e;
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-                    if (m == 0ull) continue;
-                    unsigned base = 0;
-                    if (lane == __builtin_ctzll(m)) base = atomicAdd(&hit_n, (unsigned)__builtin_popcountll(m));
-                    base = (unsigned)__builtin_amdgcn_readlane((int)base, __builtin_ctzll(m));
-                    if (hit) {
-                        const unsigned slot = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                        if (slot < HIT_CAP) { hit_lk[slot] = make_uint2((unsigned)l, key); hit_q[slot] = (unsigned short)q; }
-                    }
-                }
-            }
-            __syncthreads();
-            const unsigned n = hit_n;
-            if (tid == 0) {
-                unsigned b = 0;
-                if (n > 0) b = atomicAdd(pool_count, n < HIT_CAP ? n : HIT_CAP);
-                if (n > HIT_CAP || (n > 0 && b + n > pool_cap)) atomicOr(fail, 1u);
-                hit_base = b;
-            }
-            __syncthreads();
-            const unsigned b = hit_base, nn = n < HIT_CAP ? n : HIT_CAP;
-            for (unsigned i = tid; i < nn; i += 256)
-                if (b + i < pool_cap) { pool_lk[b + i] = hit_lk[i]; pool_q[b + i] = hit_q[i]; }
-            __syncthreads();                                          // the staging area goes back to the chunk stream
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -564,39 +507,7 @@ __global__ __launch_bounds__(256, 2) void dph_coarse_filter_gemm_kernel(int n_q,
 #undef CF_FETCH_A
 }
 
-// ---- the filter GEMM, third form (tuning key "coarse_filter" = 3): the centroids never touch LDS.
-// One workgroup of 8 waves per CU; a tile is 256 lists, wave w multiplies lists 32 w .. 32 w + 31 of it with all (<= 128) query rows.
-// The centroid image is FRAGMENT-MAJOR -- [tile][wave][k-step of 16][lane][8 bf16]: lane l of wave w loads, for k-step ks, the 16 bytes
-// the MFMA wants from it (list 32 w + (l & 31), k = 16 ks + 8 (l >> 5) ..), so every load instruction of a wave is one contiguous
-// kilobyte, a wave's share of a tile 48 KiB in one run -- straight into MFMA operand registers: a ring of three k-chunks of 128 (two in
-// flight, one being multiplied).  Only the QUERY chunk goes through LDS (double-buffered, ONE barrier per chunk), staged once per 256
-// lists: a quarter of the LDS stores of the forms above, which staged 32 KiB of centroids and the same 32 KiB of queries again per 128
-// lists -- and a ds_write_b128 costs ~54 cycles of matrix-pipe bubble (dph_scan.hip): the suspect for their 4 TB/s.
-#define CF2_LISTS 256
-#define CF2_THREADS 512
-__host__ __device__ inline int64_t dph_cf_frag_index(int64_t row, int k) {
-    const int64_t tile = row / CF2_LISTS;
-    const int w = (int)(row % CF2_LISTS) / 32, r = (int)(row % 32), ks = k / 16, h = (k % 16) / 8, e = k % 8;
-    return ((((tile * 8 + w) * (DPH_DIM / 16) + ks) * 64) + (h * 32 + r)) * 8 + e;
-}
-__global__ __launch_bounds__(256) void dph_bf16_frag_kernel(const float* __restrict__ v, int64_t n_rows, int64_t n_rows_padded,
-                                                            unsigned short* __restrict__ out) {
-    const int64_t n_elems = n_rows_padded * DPH_DIM;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_elems; i += (int64_t)gridDim.x * 256) {
-        const int64_t row = i / DPH_DIM;
-        const int k = (int)(i % DPH_DIM);
-        out[dph_cf_frag_index(row, k)] = row < n_rows ? bf16_rne(v[i]) : (unsigned short)0;
-    }
-}
-int64_t dph_bf16_frag_rows(int64_t n_rows) { return (n_rows + CF2_LISTS - 1) / CF2_LISTS * CF2_LISTS; }
-void dph_launch_bf16_frag(const float* v, int64_t n_rows, unsigned short* out, hipStream_t st) {
-    const int64_t n_elems = dph_bf16_frag_rows(n_rows) * DPH_DIM;
-    if (n_elems > 0)
-        hipLaunchKernelGGL(dph_bf16_frag_kernel, dim3((unsigned)std::min<int64_t>((n_elems + 255) / 256, 1 << 16)), dim3(256), 0, st, v, n_rows,
-                           dph_bf16_frag_rows(n_rows), out);
-}
-
-// ---- the filter as a SCAN (tuning key "coarse_filter" = 5; dph_scan.hip MODE 3): the centroids as 24 KiB pieces with the byte layout
+// ---- the filter as a SCAN (dph_scan.hip MODE 3): the centroids as 24 KiB pieces with the byte layout
 // of an int8 tile -- [tile of 32 lists][half of k][32 rows][384 bf16] -- streamed by the flat scan's feed at the flat scan's rate.
 __global__ __launch_bounds__(256) void dph_bf16_pieces_kernel(const float* __restrict__ v, int64_t n_rows, int64_t n_rows_padded,
                                                               unsigned short* __restrict__ out) {
@@ -627,195 +538,11 @@ __global__ __launch_bounds__(256) void dph_cf_qfrag_kernel(const unsigned short*
     const int q = 32 * g + (lane & 31), k = 384 * half + 16 * ks + 8 * (lane >> 5);
     qfrag[i] = q < n_q ? *(const uint4*)(x_hi + (int64_t)q * DPH_DIM + k) : make_uint4(0u, 0u, 0u, 0u);
 }
-// the chunks the scan claimed from its pair pool -> the linear (list, key) / query row pool the bucket step reads
-__global__ __launch_bounds__(256) void dph_cf_flatten_kernel(const uint2* __restrict__ pairs, const unsigned* __restrict__ chunk_fill,
-                                                             const int* __restrict__ counters, uint2* __restrict__ pool_lk,
-                                                             unsigned short* __restrict__ pool_q, unsigned* __restrict__ pool_count,
-                                                             unsigned pool_cap, unsigned* __restrict__ fail, unsigned q_base) {
-    // a chunk per WAVE and trip (lane 0 reserves the run, the wave copies it): a chunk per workgroup and trip with two barriers around
-    // the atomic was 6-8 dependent global round trips per workgroup, 26 us for the ~1500 chunks of a pass of 128 rows
-    const unsigned claimed = (unsigned)counters[1];
-    const unsigned used = claimed < (unsigned)DPH_POOL_CHUNKS ? claimed : (unsigned)DPH_POOL_CHUNKS;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (claimed > (unsigned)DPH_POOL_CHUNKS || counters[2] != 0)) atomicOr(fail, 1u);
-    const unsigned lane = threadIdx.x & 63u, gw = blockIdx.x * 4u + (threadIdx.x >> 6), n_waves = gridDim.x * 4u;
-    for (unsigned ch = gw; ch < used; ch += n_waves) {
-        const unsigned raw = chunk_fill[ch];
-        const unsigned n = raw < (unsigned)DPH_CHUNK_PAIRS ? raw : (unsigned)DPH_CHUNK_PAIRS;
-        if (n == 0) continue;
-        unsigned b = 0;
-        if (lane == 0) {
-            b = atomicAdd(pool_count, n);
-            if (b + n > pool_cap) atomicOr(fail, 1u);
-        }
-        b = (unsigned)__builtin_amdgcn_readfirstlane((int)b);
-#pragma unroll
-        for (unsigned i0 = 0; i0 < (unsigned)DPH_CHUNK_PAIRS; i0 += 64u) {
-            const unsigned i = i0 + lane;
-            if (i < n && b + i < pool_cap) {
-                const uint2 pr = pairs[(size_t)ch * DPH_CHUNK_PAIRS + i];
-                pool_lk[b + i] = make_uint2(pr.x & 0xFFFFFu, pr.y);
-                pool_q[b + i] = (unsigned short)(q_base + (pr.x >> 20));
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(CF2_THREADS, 1) void dph_coarse_filter_gemm2_kernel(int n_q, int n_lists, const unsigned short* __restrict__ c_frag,
-                                                                                const unsigned short* __restrict__ x_hi,
-                                                                                const unsigned* __restrict__ est, uint2* __restrict__ pool_lk,
-                                                                                unsigned short* __restrict__ pool_q, unsigned* __restrict__ pool_count,
-                                                                                unsigned pool_cap, unsigned* __restrict__ fail, int contiguous) {
-    constexpr int CK = CF_K, LD = CK + 8, NCH = DPH_DIM / CK, KS = CK / 16;      // 128, 136, 6 chunks per tile, 8 k-steps per chunk
-    constexpr unsigned HIT_CAP = (unsigned)CF_HIT_CAP;
-    extern __shared__ __attribute__((aligned(16))) unsigned short cf2_lds[];      // b[2][128][LD] | hit list
-    unsigned short* const b_s = cf2_lds;
-    uint2* const hit_lk = (uint2*)(cf2_lds + 2 * CG_QROWS * LD);
-    unsigned short* const hit_q = (unsigned short*)(hit_lk + HIT_CAP);
-    __shared__ unsigned hit_n;
-    __shared__ unsigned hit_base;
-    const int qb0 = blockIdx.y * CG_QROWS;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_tiles = (n_lists + CF2_LISTS - 1) / CF2_LISTS;
-    // the tiles of this workgroup: every gridDim.x-th one, or (contiguous) a run of ceil(n_tiles / gridDim.x) consecutive tiles -- each CU
-    // then walks its own window of the image front to back, like the scan kernel walks its segments
-    const int per = (n_tiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int tile0 = contiguous ? (int)blockIdx.x * per : (int)blockIdx.x, tstep = contiguous ? 1 : (int)gridDim.x;
-    const int my_tiles = contiguous ? max(0, min(per, n_tiles - tile0)) : ((int)blockIdx.x < n_tiles ? (n_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0);
-    const int n_chunks = my_tiles * NCH;
-    if (n_chunks == 0) return;
-    v16f acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    // centroid chunks: three register sets of 8 k-steps (named, constant indices only: see the scratch lesson above)
-    cf_v4u a0[KS], a1[KS], a2[KS];
-    cf_v4u rb[4];                                                  // this thread's 64 bytes of the next query chunk (512 threads x 64 B = 32 KiB)
-    const int brow = tid >> 2, bcol = tid & 3;                     // query row of the chunk, quarter of its 256 bytes
-#define CF2_FETCH_A(RA, C)                                                                                                       \
-    do {                                                                                                                         \
-        const int c_ = (C);                                                                                                      \
-        const int64_t tile_ = (int64_t)tile0 + (int64_t)(c_ / NCH) * tstep;                                                      \
-        const cf_v4u* src_ = (const cf_v4u*)(c_frag + (((tile_ * 8 + wave) * (DPH_DIM / 16) + (c_ % NCH) * KS) * 64) * 8) + lane; \
-        _Pragma("unroll") for (int i = 0; i < KS; ++i) RA[i] = __builtin_nontemporal_load(src_ + i * 64);                         \
-    } while (0)
-    auto fetch_b = [&](int c) __attribute__((always_inline)) {
-        const int k0 = (c % NCH) * CK, q = qb0 + brow;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            rb[i] = q < n_q ? *(const cf_v4u*)(x_hi + (int64_t)q * DPH_DIM + k0 + 32 * bcol + 8 * i) : cf_v4u{0u, 0u, 0u, 0u};
-    };
-    auto stage_b = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *(cf_v4u*)(b_s + (buf * CG_QROWS + brow) * LD + 32 * bcol + 8 * i) = rb[i];
-    };
-    auto epilogue = [&](int tile) __attribute__((always_inline)) {
-        if (tid == 0) hit_n = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = qb0 + j * 32 + (lane & 31);
-            const unsigned e = q < n_q ? est[q] : 0xFFFFFFFFu;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int l = tile * CF2_LISTS + wave * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                const unsigned key = f32_key(acc[j][r]);
-                const bool hit = q < n_q && l < n_lists && key >= e;
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-                if (m == 0ull) continue;
-                unsigned base = 0;
-                if (lane == __builtin_ctzll(m)) base = atomicAdd(&hit_n, (unsigned)__builtin_popcountll(m));
-                base = (unsigned)__builtin_amdgcn_readlane((int)base, __builtin_ctzll(m));
-                if (hit) {
-                    const unsigned slot = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    if (slot < HIT_CAP) { hit_lk[slot] = make_uint2((unsigned)l, key); hit_q[slot] = (unsigned short)q; }
-                }
-            }
-        }
-        __syncthreads();
-        const unsigned n = hit_n;
-        if (tid == 0) {
-            unsigned b = 0;
-            if (n > 0) b = atomicAdd(pool_count, n < HIT_CAP ? n : HIT_CAP);
-            if (n > HIT_CAP || (n > 0 && b + n > pool_cap)) atomicOr(fail, 1u);
-            hit_base = b;
-        }
-        __syncthreads();
-        const unsigned b = hit_base, nn = n < HIT_CAP ? n : HIT_CAP;
-        for (unsigned i = tid; i < nn; i += CF2_THREADS)
-            if (b + i < pool_cap) { pool_lk[b + i] = hit_lk[i]; pool_q[b + i] = hit_q[i]; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    };
-    // chunk C (k-chunk KC of its tile, both known at compile time modulo the tile) out of register set RA and LDS buffer KC & 1; the centroid
-    // chunk two steps on goes into the set two steps on, the query chunk one step on into the other LDS buffer -- whose last readers left at
-    // the barrier that ended the previous step
-#define CF2_STEP(RA, RA2, C, KC)                                                                                                 \
-    do {                                                                                                                         \
-        const int cc_ = (C);                                                                                                     \
-        if (cc_ + 2 < n_chunks) CF2_FETCH_A(RA2, cc_ + 2);                                                                        \
-        if (cc_ + 1 < n_chunks) { stage_b(((KC) + 1) & 1); if (cc_ + 2 < n_chunks) fetch_b(cc_ + 2); }                            \
-        const unsigned short* bp_ = b_s + (((KC) & 1) * CG_QROWS + (lane & 31)) * LD + 8 * (lane >> 5);                          \
-        _Pragma("unroll") for (int i = 0; i < KS; ++i) {                                                                         \
-            const v8s a_ = __builtin_bit_cast(v8s, RA[i]);                                                                       \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                      \
-                const v8s b_ = *(const v8s*)(bp_ + j * 32 * LD + 16 * i);                                                        \
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_, b_, acc[j], 0, 0, 0);                                       \
-            }                                                                                                                    \
-        }                                                                                                                        \
-        __syncthreads();                                                                                                         \
-    } while (0)
-    // prologue: centroid chunks 0 and 1 in flight, query chunk 0 staged, query chunk 1 in registers
-    CF2_FETCH_A(a0, 0);
-    CF2_FETCH_A(a1, 1);
-    fetch_b(0);
-    stage_b(0);
-    fetch_b(1);
-    __syncthreads();
-    for (int c = 0; c < n_chunks; c += NCH) {                        // one tile per trip: k-chunks 0 .. 5, register sets 0 1 2 0 1 2
-        CF2_STEP(a0, a2, c + 0, 0);
-        CF2_STEP(a1, a0, c + 1, 1);
-        CF2_STEP(a2, a1, c + 2, 2);
-        CF2_STEP(a0, a2, c + 3, 3);
-        CF2_STEP(a1, a0, c + 4, 4);
-        CF2_STEP(a2, a1, c + 5, 5);
-        epilogue(tile0 + (c / NCH) * tstep);
-    }
-#undef CF2_STEP
-#undef CF2_FETCH_A
-}
 
 #define CB_THREADS 512
-// pool -> per-row candidate lists [row][cand_cap] (list, key) + counts.  Every workgroup takes a contiguous slice of the pool, counts its
-// rows in LDS, reserves each row's run with one global atomic and scatters: n_wg x rows atomics instead of one per triple.
-__global__ __launch_bounds__(CB_THREADS) void dph_coarse_bucket_kernel(const uint2* __restrict__ pool_lk, const unsigned short* __restrict__ pool_q,
-                                                                       const unsigned* __restrict__ pool_count, unsigned pool_cap, int n_q,
-                                                                       uint2* __restrict__ cand_glob, unsigned* __restrict__ cand_cnt, int cand_cap) {
-    __shared__ unsigned cnt[DPH_PASS_MAX];
-    __shared__ unsigned base[DPH_PASS_MAX];
-    const int tid = threadIdx.x;
-    unsigned n = *pool_count;
-    if (n > pool_cap) n = pool_cap;
-    const unsigned per = (n + gridDim.x - 1) / gridDim.x;
-    const unsigned lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
-    for (int i = tid; i < n_q; i += CB_THREADS) cnt[i] = 0;
-    __syncthreads();
-    for (unsigned i = lo + tid; i < hi; i += CB_THREADS) atomicAdd(&cnt[pool_q[i]], 1u);
-    __syncthreads();
-    for (int i = tid; i < n_q; i += CB_THREADS) { base[i] = cnt[i] ? atomicAdd(&cand_cnt[i], cnt[i]) : 0u; cnt[i] = 0; }
-    __syncthreads();
-    for (unsigned i = lo + tid; i < hi; i += CB_THREADS) {
-        const unsigned q = pool_q[i];
-        const unsigned slot = base[q] + atomicAdd(&cnt[q], 1u);
-        if (slot < (unsigned)cand_cap) cand_glob[(int64_t)q * cand_cap + slot] = pool_lk[i];
-    }
-}
-
-// The same straight from the chunks the filter SCAN claimed (variant 5): no linear pool in between (dph_cf_flatten_kernel, 27 us for a
-// pass of 128 rows: ~2500 returning atomics on one counter).  A workgroup takes a contiguous range of chunks, a wave a chunk at a time;
-// pool_count only keeps the statistic (dph_debug_pq_coarse).
+// The chunks the filter scan claimed from its pair pool -> per-row candidate lists [row][cand_cap] (list, key) + counts.  A workgroup
+// takes a contiguous range of chunks, a wave a chunk at a time; it counts its rows in LDS, reserves each row's run with one global
+// atomic and scatters: n_wg x rows atomics instead of one per pair.  pool_count only keeps the statistic (dph_debug_pq_coarse).
 __global__ __launch_bounds__(CB_THREADS) void dph_coarse_bucket_chunks_kernel(const uint2* __restrict__ pairs, const unsigned* __restrict__ chunk_fill,
                                                                               const int* __restrict__ counters, int n_q_total, unsigned q_base,
                                                                               uint2* __restrict__ cand_glob, unsigned* __restrict__ cand_cnt, int cand_cap,
@@ -1192,10 +919,8 @@ static bool ensure_chain(dph_coarse_scratch::chain_part& c) {
 static bool ensure_filter(dph_coarse_scratch::filter_part& f) {
     if (f.qfrag) return true;                       // (allocated last)
     const size_t rows = DPH_PASS_MAX;
-    // (the scan form's buffers always, whether or not the first call brings the piece image: a later call that does must find them.
-    // Wave statistics for 256 CUs; the fragments of a whole pass: the teams form)
-    const bool ok = f.sample.alloc(rows * CF_SAMPLE) == hipSuccess && f.pool_lk.alloc(rows * CS_CAND) == hipSuccess &&
-                    f.pool_q.alloc(rows * CS_CAND) == hipSuccess && f.cand.alloc(rows * CS_CAND) == hipSuccess && f.cnt.alloc(1) == hipSuccess &&
+    // (wave statistics for 256 CUs; the fragments of a whole pass: the teams form)
+    const bool ok = f.sample.alloc(rows * CF_SAMPLE) == hipSuccess && f.cand.alloc(rows * CS_CAND) == hipSuccess && f.cnt.alloc(1) == hipSuccess &&
                     f.pairs.alloc((size_t)DPH_POOL_CHUNKS * DPH_CHUNK_PAIRS) == hipSuccess && f.chunk_fill.alloc(DPH_POOL_CHUNKS) == hipSuccess &&
                     f.wave_counts.alloc(256 * 4 * 2) == hipSuccess && f.counters.alloc(64) == hipSuccess &&
                     f.qfrag.alloc((size_t)(DPH_PASS_MAX / DPH_QROWS) * 4 * 2 * DPH_QGROUP_FRAG_BYTES / sizeof(uint4)) == hipSuccess;
@@ -1238,12 +963,13 @@ void dph_launch_coarse(const dph_coarse_args& a, dph_coarse_scratch& s, hipStrea
                            (const uint4*)a.listmask, (uint4*)a.tilemask, a.gate, a.gate_base);
 }
 
-// The filter form for long quantizers (comment above dph_coarse_filter_gemm_kernel).  a.x: the (rotated) query rows of the pass
-// [n_q][768] fp32, x_hi / c_hi their and the centroids' bf16 images, x_pk / c_pk the packed hi|lo images the fail-over chain multiplies.
+// The filter in front of the chain for long quantizers (comment above dph_coarse_sample_gemm_kernel).  a.x: the (rotated) query rows of
+// the pass [n_q][768] fp32, x_hi their bf16 image, c_hi / c_pieces the centroids' (chunk-major for the sample GEMM, piece-major for the
+// scan), x_pk / c_pk the packed hi|lo images the fail-over chain multiplies.
 void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratch& s, hipStream_t st) {
     dph_coarse_args chain = a;                      // what the bf16x3 chain serves: the pass as it stands, or its fail-over
     const int n_q = a.n_q, nlist = a.nlist;
-    if (!ensure_filter(s.filter) || n_q > DPH_PASS_MAX) {          // no scratch: the bf16x3 chain alone
+    if (!a.c_pieces || !ensure_filter(s.filter) || n_q > DPH_PASS_MAX) {      // no image or no scratch: the bf16x3 chain alone
         dph_launch_coarse(chain, s, st);
         return;
     }
@@ -1255,17 +981,12 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
     unsigned* const fail = &cnt->fail;
     const int m = nlist < CF_SAMPLE ? nlist : CF_SAMPLE;
     const int stride = nlist / m;
-    const unsigned pool_cap = (unsigned)((size_t)n_q * CS_CAND);
     if (a.listmask) (void)hipMemsetAsync(a.listmask, 0, (size_t)nlist * a.mask_words * 4, st);       // (NULL: the caller walks probe_out only)
     (void)hipMemsetAsync(cnt, 0, sizeof *cnt, st);
     const int dev = dph_current_device();
     const int cus = dph_scan_grid(dev);             // (at most 256: what the wave statistics hold)
     const size_t lds128 = (size_t)2 * CG_LISTS * (CF_K + 8) * 2;
-    const size_t lds_v3 = (size_t)2 * CG_QROWS * (CF_K + 8) * 2 + (size_t)CF_HIT_CAP * 10;
-    DPH_ALLOW_LDS(dph_coarse_filter_gemm_kernel<true>, lds128, dev);
-    DPH_ALLOW_LDS(dph_coarse_filter_gemm_kernel<false>, lds128, dev);
-    DPH_ALLOW_LDS((dph_coarse_filter_gemm_kernel<false, true>), lds128, dev);
-    DPH_ALLOW_LDS(dph_coarse_filter_gemm2_kernel, lds_v3, dev);
+    DPH_ALLOW_LDS(dph_coarse_sample_gemm_kernel, lds128, dev);
     cs_select_allow_lds(dev);
     const int qt = (n_q + CG_QROWS - 1) / CG_QROWS;
     const int np = a.nprobe < nlist ? a.nprobe : nlist;
@@ -1275,49 +996,28 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
     const int tiles_s = (m + CG_LISTS - 1) / CG_LISTS, tiles_f = (nlist + CG_LISTS - 1) / CG_LISTS;
     // persistent: two workgroups per CU share the list tiles (fewer when the pass has several query tiles: grid.y)
     const int wg = std::max(1, 2 * cus / qt);
-    hipLaunchKernelGGL(dph_coarse_filter_gemm_kernel<true>, dim3(std::min(tiles_s, wg), qt), dim3(256), lds128, st, n_q, m, stride, (int64_t)tiles_f, a.c_hi, a.x_hi,
-                       f.sample.p, (const unsigned*)nullptr, (uint2*)nullptr, (unsigned short*)nullptr, (unsigned*)nullptr, 0u, (unsigned*)nullptr);
+    hipLaunchKernelGGL(dph_coarse_sample_gemm_kernel, dim3(std::min(tiles_s, wg), qt), dim3(256), lds128, st, n_q, m, stride, (int64_t)tiles_f, a.c_hi, a.x_hi,
+                       f.sample.p);
     hipLaunchKernelGGL(dph_coarse_estimate_sample_kernel, dim3(n_q), dim3(CS_THREADS), 0, st, f.sample.p, n_q, m, stride, target, est);
     auto profiled = [&](auto launch) { if (a.prof) a.prof->bracket(a.prof_list, st, launch); else launch(); };
-    if (a.variant == 5 && a.c_pieces) {
-        // 128 query rows per read of the centroid image (one group of 32 per scan wave); a pass of more rows reads it once per 128 --
-        // 4 x 0.27 ms against the GEMM's 1.36 ms at 512 rows.
-        // More than 128 rows: ONE launch of teams (dph_scan.hip MODE 4) -- the groups of 128 rows share every tile through the XCDs' L2
-        // instead of each reading the image from HBM.  Groups rounded up to a power of two that divides the 32 workgroups of an XCD.
-        int n_groups = 1;
-        while (n_groups * (int)DPH_QROWS < n_q) n_groups *= 2;
-        const bool teams = a.teams != 0 && n_groups >= 2 && n_groups <= 8 && cus % (8 * n_groups) == 0;
-        if (teams) {
-            hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((n_groups * 4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi, n_q, f.qfrag.p, n_groups);
-            profiled([&] { dph_launch_coarse_scan_teams(a.c_pieces, nlist, f.qfrag, n_q, n_groups, est, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st); });
-            hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
-                               n_q, 0u, f.cand.p, cand_cnt, (int)CS_CAND, pool_count, fail);
-        }
-        for (int q0 = 0; !teams && q0 < n_q; q0 += DPH_QROWS) {
-            const int nq = std::min(n_q - q0, (int)DPH_QROWS);
-            hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi + (int64_t)q0 * DPH_DIM, nq, f.qfrag.p);
-            profiled([&] { dph_launch_coarse_scan(a.c_pieces, nlist, f.qfrag, nq, est + q0, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st); });
-            // straight into the per-row candidate lists; DPH_CF_KEEP_POOL=1 (tools/debug_coarse_scan.py) writes the linear pool of the GEMM forms too
-            static const bool keep_pool = getenv("DPH_CF_KEEP_POOL") && atoi(getenv("DPH_CF_KEEP_POOL")) != 0;
-            if (keep_pool)
-                hipLaunchKernelGGL(dph_cf_flatten_kernel, dim3(256), dim3(256), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
-                                   f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail, (unsigned)q0);
-            hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
-                               n_q, (unsigned)q0, f.cand.p, cand_cnt, (int)CS_CAND, keep_pool ? &cnt->sink : pool_count, fail);
-        }
-    } else {
-        profiled([&] {
-            if (a.variant >= 3 && a.c_frag)
-                hipLaunchKernelGGL(dph_coarse_filter_gemm2_kernel, dim3(std::min((nlist + CF2_LISTS - 1) / CF2_LISTS, std::max(1, cus / qt)), qt), dim3(CF2_THREADS), lds_v3, st,
-                                   n_q, nlist, a.c_frag, a.x_hi, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail, a.variant == 4 ? 1 : 0);
-            else if (a.variant >= 2)
-                hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, true>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
-                                   (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
-            else
-                hipLaunchKernelGGL((dph_coarse_filter_gemm_kernel<false, false>), dim3(std::min(tiles_f, wg), qt), dim3(256), lds128, st, n_q, nlist, 1, (int64_t)tiles_f, a.c_hi, a.x_hi,
-                                   (float*)nullptr, est, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, fail);
-        });
-        hipLaunchKernelGGL(dph_coarse_bucket_kernel, dim3(64), dim3(CB_THREADS), 0, st, f.pool_lk.p, f.pool_q.p, pool_count, pool_cap, n_q, f.cand.p, cand_cnt, (int)CS_CAND);
+    // 128 query rows per read of the centroid image (one group of 32 per scan wave); a pass of more rows reads it once per 128.
+    // More than 128 rows: ONE launch of teams (dph_scan.hip MODE 4) -- the groups of 128 rows share every tile through the XCDs' L2
+    // instead of each reading the image from HBM.  Groups rounded up to a power of two that divides the 32 workgroups of an XCD.
+    int n_groups = 1;
+    while (n_groups * (int)DPH_QROWS < n_q) n_groups *= 2;
+    const bool teams = a.teams != 0 && n_groups >= 2 && n_groups <= 8 && cus % (8 * n_groups) == 0;
+    if (teams) {
+        hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((n_groups * 4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi, n_q, f.qfrag.p, n_groups);
+        profiled([&] { dph_launch_coarse_scan_teams(a.c_pieces, nlist, f.qfrag, n_q, n_groups, est, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st); });
+        hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
+                           n_q, 0u, f.cand.p, cand_cnt, (int)CS_CAND, pool_count, fail);
+    }
+    for (int q0 = 0; !teams && q0 < n_q; q0 += DPH_QROWS) {
+        const int nq = std::min(n_q - q0, (int)DPH_QROWS);
+        hipLaunchKernelGGL(dph_cf_qfrag_kernel, dim3((4 * 2 * 24 * 64 + 255) / 256), dim3(256), 0, st, a.x_hi + (int64_t)q0 * DPH_DIM, nq, f.qfrag.p);
+        profiled([&] { dph_launch_coarse_scan(a.c_pieces, nlist, f.qfrag, nq, est + q0, f.pairs, f.chunk_fill, f.wave_counts, f.counters, cus, st); });
+        hipLaunchKernelGGL(dph_coarse_bucket_chunks_kernel, dim3(64), dim3(CB_THREADS), 0, st, (const uint2*)f.pairs, (const unsigned*)f.chunk_fill, (const int*)f.counters,
+                           n_q, (unsigned)q0, f.cand.p, cand_cnt, (int)CS_CAND, pool_count, fail);
     }
     hipLaunchKernelGGL(dph_coarse_select_kernel, dim3(n_q), dim3(CS_THREADS), CS_LDS, st, a.x, 0, n_q, (const int*)nullptr, 0, a.centroids,
                        (const float*)nullptr, nlist, a.nprobe, a.cnorm_max, a.listmask, a.mask_words, a.probe_out, a.probe_stride, 1.02 * CF_HI_ERR,
@@ -1330,26 +1030,12 @@ void dph_launch_coarse_filter(const dph_coarse_filter_args& a, dph_coarse_scratc
     dph_launch_coarse(chain, s, st);
 }
 
-// what the filter form did in the last pass over this scratch: out[0] = 1 when the pass failed over to the bf16x3 chain, out[1] = triples
-// its GEMM epilogue put into the pool (synchronises the device)
+// what the filter form did in the last pass over this scratch: out[0] = 1 when the pass failed over to the bf16x3 chain, out[1] = pairs
+// its scan put into the pair pool (synchronises the device)
 int dph_coarse_filter_debug(const dph_coarse_scratch& s, unsigned out[2]) {
     const dph_coarse_counters* const cnt = s.filter.cnt;
     if (!cnt) { out[0] = out[1] = 0xFFFFFFFFu; return 0; }
     return hipMemcpy(&out[0], &cnt->fail, 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&out[1], &cnt->pool_count, 4, hipMemcpyDeviceToHost) != hipSuccess;
-}
-
-// the candidate pool the filter left behind: (list, key) and query row of up to `cap` triples; returns the pool count (-1: copy failed)
-long long dph_coarse_filter_debug_pool(const dph_coarse_scratch& s, unsigned* lk_host, unsigned short* q_host, long long cap) {
-    const dph_coarse_scratch::filter_part& f = s.filter;
-    if (!f.cnt) return 0;
-    unsigned n = 0;
-    if (hipMemcpy(&n, &f.cnt.p->pool_count, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    const long long m = (long long)n < cap ? (long long)n : cap;
-    if (m > 0) {
-        if (hipMemcpy(lk_host, f.pool_lk, (size_t)m * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        if (hipMemcpy(q_host, f.pool_q, (size_t)m * 2, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    }
-    return (long long)n;
 }
 
 // ---- work queue of the unit scan (dph_internal.h: DPH_PASS_MAX).  One wave per inverted list: the probing query rows

@@ -45,7 +45,7 @@ __device__ __forceinline__ float pq_unkey(unsigned k) {
 // ---------------------------------------------------------------------------------------------- x' = A x (+ b)
 // At = A transposed ([d_in][d_out]): lane j walks column j, coalesced over the lanes, t ascending
 // out_hi / out_pk (optional): the row once more as bf16 and as packed bf16 hi << 16 | lo -- the operands of the coarse quantizer's
-// filter GEMM and of its bf16x3 fail-over chain (dph_ivf.hip), written here instead of by two more launches
+// filter and of its bf16x3 fail-over chain (dph_ivf.hip), written here instead of by two more launches
 __device__ __forceinline__ unsigned short pq_bf16_rne(float v) {
     const unsigned u = __float_as_uint(v);
     return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
@@ -317,7 +317,6 @@ struct pq_scan_args {
     const int2* pairs; const int* n_pairs; int* next; int pair_cap;
     int M; int seg; int k; int by_residual;
     unsigned* bound; unsigned* cand_count; uint2* cand; int cand_cap; unsigned* overflow;
-    int split_lut;                  // row-major scan: the last sixteen tables are read from global memory (pq_adc_sum1 GL)
     const int2* units; const int* n_units; int unit_cap;      // row-major scan: (row * units_per_row + group, segment) records of pq_units_kernel
     unsigned long long* prof;       // debugging (dph_debug_pq_phases): 8 words per workgroup of the row-major scan, null otherwise
 };
@@ -401,23 +400,10 @@ __device__ __forceinline__ void pq_adc_sum2(const uint4 (&c0)[NG], const uint4 (
 
 // One code: the sixteen table entries of a uint4 of code bytes are read TOGETHER, then added in order (the same sequential fp32 sum).
 // Left to the scheduler every ds_read was followed by s_waitcnt lgkmcnt(0) and its add -- 96 exposed LDS latencies per code.
-template <int NG, bool GL>
-__device__ __forceinline__ float pq_adc_sum1(const uint4 (&c)[NG], int ng, const float* lut_s, const float* __restrict__ lut_g, float acc) {
-    // GL (M = 96 only, tuning key "pq_split_lut", OFF by default): the sixteen entries of the LAST uint4 (m = 80 .. 95) come from the
-    // table's copy in global memory -- through the vector L1, a data path of its own -- while the LDS serves the other eighty: the LDS
-    // is the bottleneck of this loop (6 cycles per gather instruction, 65 % of them bank-conflict replays) and a sixth of its work
-    // would leave it.  Same values, same order -- but measured slower: 64 divergent dwords cost the texture path more than the bank
-    // conflicts cost the LDS (look-up sums 148 us per workgroup against 124, 0.754 ms per batch against 0.724).  Kept as the record.
-    float vg[16];
-    if constexpr (GL) {
-        const unsigned w[4] = {c[NG - 1].x, c[NG - 1].y, c[NG - 1].z, c[NG - 1].w};
+template <int NG>
+__device__ __forceinline__ float pq_adc_sum1(const uint4 (&c)[NG], int ng, const float* lut_s, float acc) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) vg[q * 4 + b] = lut_g[((NG - 1) * 16 + q * 4 + b) * 256 + ((w[q] >> (8 * b)) & 255u)];
-    }
-#pragma unroll
-    for (int g = 0; g < (GL ? NG - 1 : NG); ++g) {
+    for (int g = 0; g < NG; ++g) {
         if (g < ng) {
             const unsigned w[4] = {c[g].x, c[g].y, c[g].z, c[g].w};
             float v[16];
@@ -430,10 +416,6 @@ __device__ __forceinline__ float pq_adc_sum1(const uint4 (&c)[NG], int ng, const
             for (int i = 0; i < 16; ++i) acc = __fadd_rn(acc, v[i]);
             __builtin_amdgcn_sched_barrier(0);
         }
-    }
-    if constexpr (GL) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc = __fadd_rn(acc, vg[i]);
     }
     return acc;
 }
@@ -555,8 +537,6 @@ __global__ __launch_bounds__(PQ_THREADS, 1) void pq_adc_rows_kernel(pq_scan_args
         const int2 urec = a.units[u];
         const int r = urec.x / units_per_row, g0 = (urec.x - r * units_per_row) * PQ_GROUP;
         const float4* src = (const float4*)(a.lut + (size_t)r * M * 256);
-        const float* const lut_g = a.lut + (size_t)r * M * 256;
-        const bool gl = a.split_lut && M == NG * 16;            // (wave-uniform)
         for (int i = tid; i < M * 64; i += PQ_THREADS) ((float4*)lut_s)[i] = src[i];
         if (tid < PQ_GROUP) {
             const int l = g0 + tid < probe_stride ? probe[(size_t)r * probe_stride + g0 + tid] : -1;
@@ -630,11 +610,7 @@ __global__ __launch_bounds__(PQ_THREADS, 1) void pq_adc_rows_kernel(pq_scan_args
                     const int jc = jn;
                     if (i + PQ_THREADS < n) pq_load_code(a.codes, locate(s0 + i + PQ_THREADS, jn), M, M / 16, cn);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (NG == 6) {           // (the released OPQ96; the M = 128 build has no registers to spare)
-                        keys_s[i] = pq_key(gl ? pq_adc_sum1<NG, true>(cc, NG, lut_s, lut_g, g_dis0[jc]) : pq_adc_sum1<NG, false>(cc, M / 16, lut_s, lut_g, g_dis0[jc]));
-                    } else {
-                        keys_s[i] = pq_key(pq_adc_sum1<NG, false>(cc, M / 16, lut_s, lut_g, g_dis0[jc]));
-                    }
+                    keys_s[i] = pq_key(pq_adc_sum1<NG>(cc, M / 16, lut_s, g_dis0[jc]));
                 }
             }
             __syncthreads();
@@ -903,13 +879,10 @@ struct dph_pq {
     dev_buf<float> A, At, b, cent, pqc;
     dev_buf<float> pqc_bias, pqc_wmax;                     // the encoder's view of the codebooks: fp32(-||w_mj||^2 / 2) [M][256] and max_j ||w_mj|| [M] (rounded up)
     dev_buf<unsigned> cent_pk;                             // bf16 hi << 16 | lo of the centroids (long quantizers: the bf16x3 coarse GEMM)
-    dev_buf<unsigned short> cent_hi;                       // the centroids as plain bf16: the coarse quantizer's one-product filter GEMM
-    dev_buf<unsigned short> cent_frag;                     // ... once more in MFMA fragment order (filter GEMM variant 3)
-    dev_buf<unsigned short> cent_pieces;                   // ... and as 24 KiB pieces with the byte layout of an int8 tile (the filter SCAN, variant 5)
-    int split_lut = 0;                                     // tuning key "pq_split_lut": measured SLOWER (sums 148 us against 124 per workgroup), off
-    int coarse_filter = 5;                                 // 0: the bf16x3 chain alone, 1 / 2: filter GEMM staging centroids and queries through LDS (2: centroid stream
-                                                           // non-temporal), 3: centroids straight into registers from the fragment-major image, 4: 3 on contiguous tile runs,
-                                                           // 5 (default, round 5): the filter as a SCAN -- bf16 centroid pieces through the flat scan's feed (dph_scan.hip MODE 3)
+    dev_buf<unsigned short> cent_hi;                       // the centroids as plain bf16, chunk-major: the sample GEMM of the coarse quantizer's filter
+    dev_buf<unsigned short> cent_pieces;                   // ... and as 24 KiB pieces with the byte layout of an int8 tile: the filter scan
+    int coarse_filter = 1;                                 // tuning key "coarse_filter": 1 (default) = the filter scan in front of the bf16x3 chain -- bf16 centroid pieces
+                                                           // through the flat scan's feed (dph_scan.hip MODE 3) --, 0 = the chain alone
     int coarse_teams = 1;                                  // tuning key "coarse_teams": passes of more than 128 rows run the filter scan as ONE launch of workgroup teams
     dph_profiler prof;
     dph_event_pairs prof_events;                           // around the launches of the coarse filter's dominant kernel
@@ -952,21 +925,13 @@ int dph_pq_alloc(dph_pq** out, int device, int64_t ntotal, int nlist, int M) {
     return DPH_OK;
 }
 
-void dph_pq_set_split_lut(dph_pq* p, int on) { if (p) p->split_lut = on ? 1 : 0; }
-void dph_pq_set_coarse_filter(dph_pq* p, int on) { if (p) p->coarse_filter = on < 0 ? 0 : (on > 5 ? 5 : on); }
+void dph_pq_set_coarse_filter(dph_pq* p, int on) { if (p) p->coarse_filter = on ? 1 : 0; }
 void dph_pq_set_coarse_teams(dph_pq* p, int on) { if (p) p->coarse_teams = on ? 1 : 0; }
 int dph_pq_coarse_debug(dph_pq* p, unsigned out[2]) {
     if (!p) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipDeviceSynchronize());
     return dph_coarse_filter_debug(p->coarse, out) ? fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
-}
-int dph_pq_coarse_debug_pool(dph_pq* p, unsigned* lk_host, unsigned short* q_host, long long cap, long long* count) {
-    if (!p || !count) return fail(DPH_E_ARG, "null");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());
-    *count = dph_coarse_filter_debug_pool(p->coarse, lk_host, q_host, cap);
-    return *count < 0 ? fail(DPH_E_HIP, "coarse debug: copy failed") : DPH_OK;
 }
 // what the LAST pass left in the scan's bookkeeping: info[8] = {counters[0..3] (pairs, next, units, -), cand_cap, unit_cap, pair_cap, rows of
 // the scratch}, per_row[n][3] = {appended candidates, overflow flag, bound key} of the first n rows.  (tests/test_fuzz_gpu.py prints it
@@ -1055,10 +1020,8 @@ int dph_pq_set_params(dph_pq* p, const float* A, const float* b, const float* ce
     if (p->nlist >= (1 << 16)) {                    // CG_BF16X3_MIN of dph_ivf.hip: the coarse GEMM of long quantizers runs on bf16 hi / lo parts
         if (!p->cent_pk) HIPCHK(p->cent_pk.alloc((size_t)p->nlist * DPH_DIM));
         dph_launch_bf16_split(p->cent, (int64_t)p->nlist * DPH_DIM, p->cent_pk, nullptr);
-        if (!p->cent_hi) HIPCHK(p->cent_hi.alloc((size_t)dph_bf16_hi_rows(p->nlist, 1) * DPH_DIM));
-        dph_launch_bf16_hi(p->cent, p->nlist, 1, p->cent_hi, nullptr);
-        if (!p->cent_frag) HIPCHK(p->cent_frag.alloc((size_t)dph_bf16_frag_rows(p->nlist) * DPH_DIM));
-        dph_launch_bf16_frag(p->cent, p->nlist, p->cent_frag, nullptr);
+        if (!p->cent_hi) HIPCHK(p->cent_hi.alloc((size_t)dph_bf16_hi_rows(p->nlist) * DPH_DIM));
+        dph_launch_bf16_hi(p->cent, p->nlist, p->cent_hi, nullptr);
         if (!p->cent_pieces) HIPCHK(p->cent_pieces.alloc((size_t)dph_bf16_piece_rows(p->nlist) * DPH_DIM));
         dph_launch_bf16_pieces(p->cent, p->nlist, p->cent_pieces, nullptr);
         HIPCHK(hipDeviceSynchronize());
@@ -1341,14 +1304,14 @@ static dph_coarse_filter_args pq_coarse_args(dph_pq* p, int nq, int nprobe, bool
     c.probe_out = by_rows ? p->s.probe.p : nullptr; c.probe_stride = nprobe;
     c.c_pk = p->cent_pk; c.x_pk = p->cent_pk ? p->s.xp_pk.p : nullptr;
     c.row_fail = p->s.overflow();
-    // the filter form's part
-    c.c_hi = p->cent_hi; c.x_hi = p->s.xp_hi; c.c_frag = p->cent_frag; c.c_pieces = p->cent_pieces;
+    // the filter's part
+    c.c_hi = p->cent_hi; c.x_hi = p->s.xp_hi; c.c_pieces = p->cent_pieces;
     c.cnorm = p->cnorm; c.cnorm_cap = p->cnorm_cap;
-    c.variant = p->coarse_filter; c.teams = p->coarse_teams;
+    c.teams = p->coarse_teams;
     if (p->prof.on) { c.prof = &p->prof; c.prof_list = &p->prof_events; }
     return c;
 }
-// Stage 2: the counters of the pass cleared, then the coarse probe -- a long quantizer through the filter form, otherwise the chain.
+// Stage 2: the counters of the pass cleared, then the coarse probe -- a long quantizer through the filter, otherwise the chain.
 static int pq_pass_probe(dph_pq* p, int nq, int nprobe, bool by_rows, hipStream_t st) {
     HIPCHK(hipMemsetAsync(p->s.counters, 0, pq_scratch::counter_bytes(p->s.cap_rows, 3), st));
     const dph_coarse_filter_args c = pq_coarse_args(p, nq, nprobe, by_rows);
@@ -1371,7 +1334,6 @@ static void pq_pass_scan(dph_pq* p, int nq, int k, int nprobe, bool by_rows, int
     a.M = p->M; a.seg = pq_seg(p->M); a.k = k; a.by_residual = p->by_residual;
     a.bound = s.bound(); a.cand_count = s.cand_count(); a.cand = s.cand; a.cand_cap = s.cand_cap; a.overflow = s.overflow();
     a.prof = p->phase_prof && p->phase_wgs >= grid ? p->phase_prof : nullptr;
-    a.split_lut = p->split_lut;
     a.units = s.units; a.n_units = &head->n_units; a.unit_cap = s.unit_cap;
     const int upr = (nprobe + PQ_GROUP - 1) / PQ_GROUP;
     // many short lists on average: group the work by query row, cut by code count (pq_units_kernel)

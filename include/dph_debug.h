@@ -35,18 +35,15 @@ extern "C" {
  *   "scan_sched"    hand-over schedule of the flat full scan, one value for both kernels or two (128-row, 256-row kernel):
  *                   0 = every wave stages its pieces of a tile right behind the tile's barrier, 1 = one wave after the other
  *                   (default), 2 = interleaved, one wave per k-step (same results; profiles/r04_scan_scheds_170M.json)
- *   "coarse_filter" PQ index with >= 2^16 lists: 1 .. 5 = the coarse quantizer (index.py:53 nprobe lists by <x', c>) runs a
- *                   one-product bf16 filter with the threshold test in its epilogue in front of the float64 re-rank.  5 (default,
- *                   round 5): a filter SCAN -- the centroids as 24 KiB pieces with the byte layout of an int8 tile through the flat
- *                   scan's feed, 128 query rows per read (0.27 ms = 0.76 of the HBM peak for 2^20 centroids); 3: a GEMM with the
- *                   centroids straight into MFMA operand registers from a fragment-major image (0.36 ms); 1 / 2: centroids and
- *                   queries staged through LDS, 2 with non-temporal loads; 4: 3 on contiguous runs of tiles; 0 = the three-product
- *                   bf16 GEMM over the whole score matrix (the fail-over chain) alone; same probe set, same candidate pool
- *   "coarse_teams"  PQ index, filter scan (coarse_filter 5), a pass of more than 128 query rows: 1 (default) = ONE launch in which teams of
+ *   "coarse_filter" PQ index with >= 2^16 lists: 1 (default) = the coarse quantizer (index.py:53 nprobe lists by <x', c>) runs a
+ *                   one-product bf16 filter SCAN under a sampled threshold in front of the float64 re-rank -- the centroids as 24 KiB
+ *                   pieces with the byte layout of an int8 tile through the flat scan's feed, 128 query rows per read (0.27 ms =
+ *                   0.76 of the HBM peak for 2^20 centroids); 0 = the three-product bf16 GEMM over the whole score matrix (the
+ *                   fail-over chain) alone; same probe set.  5 is accepted as the old spelling of 1 (the GEMM forms 1 .. 4 of the
+ *                   filter were measured slower and removed: DESIGN_HISTORY.md); every other value is DPH_E_ARG
+ *   "coarse_teams"  PQ index, filter scan (coarse_filter 1), a pass of more than 128 query rows: 1 (default) = ONE launch in which teams of
  *                   2 / 4 / 8 workgroups of one XCD stream the same run of centroid tiles, each against its own group of 128 rows, and share
- *                   them through the XCD's L2 (the image leaves HBM once per pass); 0 = one launch -- one read of the image -- per 128 rows
- *   "pq_split_lut"  PQ index, OPQ96, row-major ADC scan: 1 = the last sixteen look-up tables are gathered from global memory instead
- *                   of LDS (an experiment to relieve the bank-conflict-bound LDS: measured slower, default 0; same results) */
+ *                   them through the XCD's L2 (the image leaves HBM once per pass); 0 = one launch -- one read of the image -- per 128 rows */
 int dph_index_set_tuning(dph_index* h, const char* key, const int32_t* values, int n_values);
 
 /* (row, query row) pairs the LAST scan launch on the handle emitted and how often a wave took its emit path */
@@ -78,7 +75,7 @@ int dph_search_prepare_dev(dph_index* h, const float* x_dev, int64_t n, int k, v
 int dph_search_finish_dev(dph_index* h, const float* x_dev, int64_t n, int k, float* D_dev, int64_t* I_dev, int32_t* status_dev,
                           void* stream);
 
-/* ---- measurement hook (bench.py): when on, every scan launch (PQ index: the coarse quantizer's filter GEMM, its dominant
+/* ---- measurement hook (bench.py): when on, every scan launch (PQ index: the coarse quantizer's filter scan, its dominant
  * kernel) is bracketed by HIP events on its stream;
  * dph_profile_read synchronises those events and returns the summed kernel time and launch count since the
  * last read (roofline: algorithmic bytes per launch / average launch duration). */
@@ -115,15 +112,13 @@ int dph_debug_scan_time(dph_index* h, const float* x, int64_t n, int iters, floa
  * than 8192 cannot be sorted, more than 32768 do not fit: "lost pairs"), overflow_out[n] != 0: the pair pool ran dry for that row.
  * With tuning key "retry_chain" = 0 the last pass is the first attempt's. */
 int dph_debug_bucket_counts(dph_index* h, int64_t n, uint32_t* raw_out, uint32_t* overflow_out);
-/* PQ index, coarse quantizer of the LAST pass searched (tuning key "coarse_filter"): out[0] = 1 when the filter form failed over to
- * the three-product chain (0xFFFFFFFF: the filter form has not run), out[1] = (row, list) candidates its GEMM epilogue emitted. */
+/* PQ index, coarse quantizer of the LAST pass searched (tuning key "coarse_filter"): out[0] = 1 when the filter failed over to
+ * the three-product chain (0xFFFFFFFF: the filter has not run), out[1] = (row, list) candidates its scan emitted. */
 int dph_debug_pq_coarse(dph_index* h, uint32_t out[2]);
 /* PQ index, bookkeeping of the LAST pass of the ADC scan: info[8] = {list-major pairs, work items taken, row-major units, 0, candidate
  * capacity per row, unit capacity, pair capacity, rows the scratch is sized for}; per_row[n_rows][3] = {candidates appended, overflow
  * flag (any stage: coarse band, work queue, candidates), the row's final bound key}.  What a row with status 1 ran into. */
 int dph_debug_pq_pass(dph_index* h, int32_t info[8], uint32_t* per_row, int n_rows);
-/* the (list, score key) pairs [cap][2] and query rows [cap] of the candidate pool that pass left behind; *count = triples in the pool */
-int dph_debug_pq_pool(dph_index* h, uint32_t* lk_host, uint16_t* q_host, int64_t cap, int64_t* count);
 /* Phase clocks of the PQ search chain, 100 MHz ticks.  The first call (out may be null) arms a clock; later calls copy what the LAST
  * launch left.  which = 0, the row-major ADC scan (many short lists): out[wg][8] = {start, end, table + list offsets, dis0, look-up
  * sums, k-th selection + append, units taken, codes summed} per workgroup, *n_wgs = workgroups of the launch; costs one barrier per

@@ -4,7 +4,7 @@ top-k, where a list wrongly swapped in or out at the nprobe-th place almost neve
 ONE row (one PQ code) per list and k = min(nprobe, nlist): the returned ids are the probed lists (tests/_coarse_sets.py), and they
 are held against ``np.lexsort((list id, -float64 score))[:k]`` row by row -- through the radix select, the one-pass estimate /
 collect path (nlist >= 8192), the fp32 error band and the float64 band re-rank with its list-id tie rule (flat-IVF path), and through
-the fp32 chain, the bf16x3 chain and every filter form of the PQ path."""
+the fp32 chain, the bf16x3 chain and the filter of the PQ path."""
 import numpy as np
 import pytest
 
@@ -192,10 +192,11 @@ def _oracle_probe(ix, x, nprobe, chunk=64):
     return np.concatenate([P.coarse_probe(xp[r0:r0 + chunk], ix.index.centroids, nprobe)[0] for r0 in range(0, len(xp), chunk)])
 
 
-# (filter form, teams, (n_q, nprobe) ...): every filter form, both team settings of the scan form, every n_q and every nprobe of the
-# issue at least once; the order statistics of the filter forms depend on nprobe, the team launch on n_q > 128
-_PQ_RANDOM_RUNS = [(5, 1, ((1024, 256), (129, 1024), (5, 1))), (5, 0, ((1024, 40), (129, 256))), (4, 1, ((129, 40), (5, 1024))),
-                   (3, 1, ((1024, 1), (5, 256))), (2, 1, ((129, 1), (5, 40))), (1, 1, ((129, 256), (1024, 1024))),
+# (filter, teams, (n_q, nprobe) ...): the filter with both team settings and the chain alone, every n_q and every nprobe of the
+# issue at least once; the order statistics of the filter depend on nprobe, the team launch on n_q > 128.  (The combinations the
+# removed GEMM forms of the filter ran are kept: those of more than 128 rows under both team settings.)
+_PQ_RANDOM_RUNS = [(1, 1, ((1024, 256), (129, 1024), (5, 1), (129, 40), (1024, 1), (129, 1), (129, 256), (1024, 1024), (5, 1024), (5, 256))),
+                   (1, 0, ((1024, 40), (129, 256), (129, 40), (1024, 1), (129, 1), (1024, 1024), (5, 40))),
                    (0, 1, ((129, 1024), (5, 40)))]
 
 
@@ -204,7 +205,7 @@ _PQ_RANDOM_RUNS = [(5, 1, ((1024, 256), (129, 1024), (5, 1))), (5, 0, ((1024, 40
 @pytest.mark.parametrize("kind", ["random", "dup", "ulp"])
 def test_pq_probe_sets_equal_the_oracles_coarse_probe(nlist, kind):
     """dph_search_ivf on an IVFPQ handle with one code per list: the returned ids are the lists of ``coarse_probe(apply_chain(q))``.
-    4096 lists take the fp32 chain; 65536 lists the bf16x3 chain (coarse_filter 0) and the filter forms 1 .. 5 (5 with and without
+    4096 lists take the fp32 chain; 65536 lists the bf16x3 chain (coarse_filter 0) and the filter in front of it (with and without
     teams), which must not fail over on these centroid sets.  Random centroids: 5 / 129 / 1024 query rows x nprobe 1 / 40 / 256 /
     1024.  Copies / one-ulp variants: 129 rows, nprobe cutting before, inside, at the end of and just past the block, and 40 / 256."""
     cent, src, block = CS.centroid_set(kind, nlist, seed=nlist // 7 + len(kind))
@@ -218,9 +219,9 @@ def test_pq_probe_sets_equal_the_oracles_coarse_probe(nlist, kind):
         runs = _PQ_RANDOM_RUNS
     else:
         combos = tuple((129, p) for p in sorted(set(CS.block_nprobes(block, nlist)) | {40, 256}))
-        runs = [(f, t, combos) for f, t in ((5, 1), (5, 0), (4, 1), (3, 1), (2, 1), (1, 1), (0, 1))]
+        runs = [(f, t, combos) for f, t in ((1, 1), (1, 0), (0, 1))]
     if nlist < 65536:                                      # no filter images below CG_BF16X3_MIN lists: one setting is all there is
-        runs = [(5, 1, tuple(sorted({c for _, _, cs in runs for c in cs})))]
+        runs = [(1, 1, tuple(sorted({c for _, _, cs in runs for c in cs})))]
     for filt, teams, combos in runs:
         s.set_tuning("coarse_filter", filt)
         s.set_tuning("coarse_teams", teams)

@@ -25,7 +25,7 @@ def _uniform_index(seed, nlist, n, M=96):
 
 @pytest.fixture(scope="module")
 def long_quantizer_shard():
-    """65536 lists: the smallest quantizer that reaches the filter forms"""
+    """65536 lists: the smallest quantizer that reaches the filter"""
     ix, rng = _uniform_index(83, 65536, 12000)
     s = _shard(ix)
     yield s, rng
@@ -34,9 +34,9 @@ def long_quantizer_shard():
 
 @pytest.mark.gpu
 def test_pq_profile_brackets_every_launch_of_the_coarse_filters_dominant_kernel(long_quantizer_shard):
-    """One event pair per launch of the filter's dominant kernel: the scan form launches once per 128 query rows, or once for the whole
-    pass when the groups run as teams (300 rows: 4 groups); the GEMM forms launch once; the bf16x3 chain alone brackets nothing.  Every
-    read hands the pairs back: a second read finds none."""
+    """One event pair per launch of the filter's dominant kernel: the scan launches once per 128 query rows, or once for the whole
+    pass when the groups run as teams (300 rows: 4 groups); the bf16x3 chain alone brackets nothing.  Every read hands the pairs back:
+    a second read finds none."""
     s, rng = long_quantizer_shard
     k, nprobe = 5, 16
     q100 = rng.normal(0, 0.5, (100, 768)).astype(np.float32)
@@ -61,9 +61,6 @@ def test_pq_profile_brackets_every_launch_of_the_coarse_filters_dominant_kernel(
         s.search_ivf(q300, k, nprobe)
         assert launches_then_none() == 3
         s.set_tuning("coarse_teams", 1)
-        s.set_tuning("coarse_filter", 3)                    # a GEMM form: the one GEMM launch
-        s.search_ivf(q300, k, nprobe)
-        assert launches_then_none() == 1
         s.set_tuning("coarse_filter", 0)                    # the bf16x3 chain alone: no filter, nothing bracketed
         s.search_ivf(q300, k, nprobe)
         assert launches_then_none() == 0
@@ -75,6 +72,30 @@ def test_pq_profile_brackets_every_launch_of_the_coarse_filters_dominant_kernel(
         s.set_tuning("coarse_teams", 1)
         s.set_tuning("coarse_filter", 5)
         s.profile_enable(False)
+
+
+@pytest.mark.gpu
+def test_pq_coarse_filter_key_accepts_0_1_and_5_and_rejects_the_removed_forms():
+    """Tuning key coarse_filter: 0 = the chain alone, 1 = the filter in front of it, 5 = the old spelling of 1.  The GEMM forms of the
+    filter are gone and a request for 2 .. 4 fails with DPH_E_ARG and a message that names the accepted values -- as does any other value --
+    instead of being served by the scan; a rejected value leaves the setting where it was (same D and I)."""
+    from densephrases_amd._lib import DphError
+    ix, rng = _uniform_index(87, 64, 64 * 200)
+    s = _shard(ix)
+    try:
+        q = rng.normal(0, 0.5, (7, 768)).astype(np.float32)
+        for v in (0, 1, 5):
+            s.set_tuning("coarse_filter", v)
+        D0, I0 = s.search_ivf(q, 10, 8)
+        for v in (2, 3, 4, 6, -1):
+            with pytest.raises(DphError) as e:
+                s.set_tuning("coarse_filter", v)
+            assert e.value.code == -1, (v, e.value)         # DPH_E_ARG
+            assert all(name in str(e.value) for name in ("coarse_filter", "0 (", "1 (", "5 (")), (v, e.value)
+            D, I = s.search_ivf(q, 10, 8)
+            assert np.array_equal(I, I0) and np.array_equal(D, D0), v
+    finally:
+        s.close()
 
 
 def _probed_codes(ix, q, nprobe):

@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--skew", default="", help="list-size skew of the synthetic index: '' (near-uniform), zipf, lognormal, giant (synth._pq_list_sizes); long lists are the most probed (--hot)")
     ap.add_argument("--hot", type=float, default=0.18)
     ap.add_argument("--phases", action="store_true", help="phase clock of the row-major ADC scan (dph_debug_pq_phases) of one more batch")
-    ap.add_argument("--tune", action="append", default=[], help="libdph tuning key=v (e.g. coarse_filter=0)")
+    ap.add_argument("--tune", action="append", default=[], help="libdph tuning key=v (e.g. coarse_filter=0: the chain alone; 1, the default: the filter scan in front of it)")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as g
