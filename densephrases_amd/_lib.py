@@ -122,6 +122,7 @@ def _load() -> C.CDLL:
         "dph_index_set_pq_list_sizes": (C.c_int, [vp, vp]),
         "dph_index_upload_pq_codes": (C.c_int, [vp, i64, i64, vp, vp]),
         "dph_index_get_transform": (C.c_int, [vp, vp]),
+        "dph_index_attach_doc_rows": (C.c_int, [vp, i64]),
         "dph_pq_encode_dev": (C.c_int, [vp, vp, i64, vp, vp, vp]),
         "dph_index_fill_pq_dev": (C.c_int, [vp, i64, vp, vp, vp, vp]),
         "dph_index_get_pq_list_sizes": (C.c_int, [vp, vp]),
@@ -151,7 +152,7 @@ EXPORTED = ["dph_abi_version", "dph_last_error", "dph_device_count", "dph_index_
             "dph_index_set_tuning", "dph_scan_counters", "dph_debug_wave_pairs", "dph_index_rehome_rows", "dph_index_gather_rows_dev", "dph_kmeans_step_dev", "dph_index_stored_rows", "dph_index_set_id_groups", "dph_ivf_assign_dev", "dph_index_assign_dev", "dph_index_make_list_major", "dph_score_vecs_dev", "dph_score_vecs_bwd_dev", "dph_dense_logits_dev",
             "dph_profile_enable", "dph_profile_read", "dph_profile_read_all", "dph_index_set_row_ids",
             "dph_index_set_ivf", "dph_search_ivf", "dph_search_ivf_dev", "dph_index_create_pq", "dph_index_set_pq",
-            "dph_index_set_pq_list_sizes", "dph_index_upload_pq_codes", "dph_index_get_transform", "dph_pq_encode_dev",
+            "dph_index_set_pq_list_sizes", "dph_index_upload_pq_codes", "dph_index_get_transform", "dph_index_attach_doc_rows", "dph_pq_encode_dev",
             "dph_index_fill_pq_dev", "dph_index_get_pq_list_sizes", "dph_index_download_pq_codes", "dph_index_create_twin",
             "dph_stream_create_cu_range", "dph_stream_destroy", "dph_search_prepare_dev", "dph_search_finish_dev"]
 
@@ -180,13 +181,14 @@ class Shard:
         self.n_rows = int(n_rows)            # stored rows (list-major shards: padding included)
 
     @classmethod
-    def from_faiss_index(cls, index, device: int = 0, chunk_codes: int = 1 << 22, keep=None):
+    def from_faiss_index(cls, index, device: int = 0, chunk_codes: int = 1 << 22, keep=None, doc_rows: int = 0):
         """A PQ index resident in HBM from a parsed FAISS file (densephrases_amd.faiss_io: PreTransformIndex over an
         IVFPQIndex, or a bare IVFPQIndex): the reference's own index type, index.py:30-33.  The codes / ids of the
         inverted lists are uploaded list by list (np.memmap views of merged.invdata are read once, in chunks).  Call
         set_idx2id / set_id_groups / set_f2o as for a raw-dump shard, then finalize().
         ``keep``: callable ids -> bool mask; only those codes of every list are uploaded -- the shard of ONE rank of a
-        range-sharded job (every rank holds the OPQ matrix, all centroids and codebooks, and the codes of its own id range)."""
+        range-sharded job (every rank holds the OPQ matrix, all centroids and codebooks, and the codes of its own id range).
+        ``doc_rows`` > 0: attach_doc_rows(doc_rows) as well -- the caller uploads the documents' raw rows before finalize()."""
         ivf = cls._ivf_of(index)
         masks = None
         if keep is not None:
@@ -210,10 +212,19 @@ class Shard:
                     i = np.ascontiguousarray(ids[o:o + chunk_codes], dtype=np.int64)
                     _chk(lib.dph_index_upload_pq_codes(self._h, pos + o, len(i), _p(c), _p(i)))
                 pos += n
+            if doc_rows:
+                self.attach_doc_rows(doc_rows)
         except Exception:
             self.close()                    # a half-loaded index holds gigabytes of HBM
             raise
         return self
+
+    def attach_doc_rows(self, n_doc_rows: int):
+        """Room for the dump's raw int8 rows next to the codes of a PQ handle (dph_index_attach_doc_rows): [n_doc_rows, 768], whole
+        documents in f2o-CSR order.  ``upload`` / ``upload_async`` then fill it, ``set_codec`` applies to it, and after ``finalize``
+        ``rescore`` follows the reference's HDF5 branch (index.py:246-273) instead of re-scoring reconstructions."""
+        _chk(lib.dph_index_attach_doc_rows(self._h, int(n_doc_rows)))
+        self.n_doc_rows = int(n_doc_rows)
 
     @staticmethod
     def _ivf_of(index):
@@ -516,8 +527,9 @@ class Shard:
         _chk(lib.dph_search_get_stats(self._h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in SearchStats._fields_}
 
-    def profile_enable(self, on: bool = True):
-        _chk(lib.dph_profile_enable(self._h, 1 if on else 0))
+    def profile_enable(self, on=True):
+        """True / False; 3 on a PQ index: the window kernels of rescore are bracketed too (profile_read_each(3))"""
+        _chk(lib.dph_profile_enable(self._h, int(on)))
 
     def profile_read(self):
         """(summed scan-kernel milliseconds, launches) since the last read; synchronises the recorded events."""

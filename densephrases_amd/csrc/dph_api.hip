@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -73,6 +74,13 @@ struct dph_shard {
     dev_buf<int32_t> row2doc, row2word;
     std::vector<int32_t> h_row2doc, h_row2word;
     dev_buf<int32_t> doc_ids; dev_buf<int64_t> f2o_off; dev_buf<int32_t> f2o; int64_t n_docs = 0;
+    int64_t f2o_total = 0;               // f2o_off[n_docs]: the words of all documents of the CSR
+    // PQ index with the dump's raw rows next to its codes (dph_index_attach_doc_rows): the int8 `start` rows of WHOLE documents in the
+    // order of the f2o CSR, row of (document slot d, word w) = f2o_off[d] + w -- what the reference's HDF5 branch reads (index.py:246-273)
+    dev_buf<int8_t> doc_rows; int64_t n_doc_rows = 0;
+    std::map<int64_t, int64_t> doc_rows_have;       // uploaded runs [first, second), merged: finalize wants exactly [0, n_doc_rows)
+    float doc_lut_host[256];             // that branch's de-quantisation: fp32(n / scale + offset), float64 rounded ONCE (index.py:158-162, 334)
+    dev_buf<float> doc_lut;
     // the reference's own index type (IndexPreTransform + IndexIVFPQ) instead of raw int8 rows: dph_pq.hip
     dph_pq* pq = nullptr;
     ~dph_shard() { if (pq) dph_pq_free(pq); }
@@ -163,6 +171,7 @@ static void build_lut(dph_shard* s) {
         s->lut_host[n + 128] = b;
         const double exact = (double)n / (double)s->scale + (double)s->offset;
         dm = fmax(dm, fabs((double)b - exact));
+        s->doc_lut_host[n + 128] = (float)exact;
     }
     s->delta_max = dm;
 }
@@ -249,23 +258,68 @@ int dph_index_set_codec(dph_index* h, float offset, float scale) {
     h->sh->offset = offset; h->sh->scale = scale;
     build_lut(h->sh);
     HIPCHK(hipMemcpy(h->sh->lut_dev, h->sh->lut_host, sizeof(h->sh->lut_host), hipMemcpyHostToDevice));
+    if (h->sh->doc_lut) HIPCHK(hipMemcpy(h->sh->doc_lut, h->sh->doc_lut_host, sizeof(h->sh->doc_lut_host), hipMemcpyHostToDevice));
+    return DPH_OK;
+}
+
+// where dph_index_upload_rows(_async) writes: the shard's rows, or -- a PQ index with document rows attached -- that store
+static int8_t* upload_target(dph_shard* s, int64_t* cap) {
+    const bool doc = s->pq && s->doc_rows;
+    *cap = doc ? s->n_doc_rows : s->n_rows;
+    return doc ? s->doc_rows.p : s->db.p;
+}
+static void note_doc_rows(dph_shard* s, int64_t row0, int64_t n) {
+    if (!(s->pq && s->doc_rows) || n <= 0) return;
+    int64_t a = row0, b = row0 + n;
+    auto it = s->doc_rows_have.upper_bound(a);
+    if (it != s->doc_rows_have.begin() && std::prev(it)->second >= a) --it;
+    while (it != s->doc_rows_have.end() && it->first <= b) {
+        a = std::min(a, it->first); b = std::max(b, it->second);
+        it = s->doc_rows_have.erase(it);
+    }
+    s->doc_rows_have[a] = b;
+}
+
+int dph_index_attach_doc_rows(dph_index* h, int64_t n_doc_rows) {
+    DPH_NOT_TWINNED(h, "dph_index_attach_doc_rows");
+    if (!h || n_doc_rows <= 0) return fail(DPH_E_ARG, "dph_index_attach_doc_rows: need a handle and n_doc_rows > 0");
+    dph_shard* const s = h->sh;
+    if (!s->pq) return fail(DPH_E_STATE, "dph_index_attach_doc_rows: not a PQ index (dph_index_create_pq)");
+    if (s->doc_rows) return fail(DPH_E_STATE, "dph_index_attach_doc_rows: document rows are attached already");
+    if (s->finalized) return fail(DPH_E_STATE, "dph_index_attach_doc_rows: attach before dph_index_finalize");
+    HIPCHK(hipSetDevice(h->device));
+    hipError_t e = s->doc_lut.alloc(256);
+    if (e == hipSuccess) e = s->doc_rows.alloc((size_t)n_doc_rows * DPH_DIM);
+    if (e != hipSuccess) {
+        s->doc_rows.reset(); s->doc_lut.reset();
+        return fail(DPH_E_NOMEM, std::string("dph_index_attach_doc_rows: hipMalloc: ") + hipGetErrorString(e));
+    }
+    HIPCHK(hipMemcpy(s->doc_lut, s->doc_lut_host, sizeof(s->doc_lut_host), hipMemcpyHostToDevice));
+    s->n_doc_rows = n_doc_rows;
+    s->doc_rows_have.clear();
     return DPH_OK;
 }
 
 int dph_index_upload_rows(dph_index* h, int64_t row0, int64_t n, const int8_t* host_rows) {
     DPH_NOT_TWINNED(h, "dph_index_upload_rows");
-    if (!h || !host_rows || row0 < 0 || n < 0 || row0 + n > h->sh->n_rows) return fail(DPH_E_ARG, "dph_index_upload_rows: range");
+    int64_t cap = 0;
+    int8_t* const dst = h ? upload_target(h->sh, &cap) : nullptr;
+    if (!h || !host_rows || row0 < 0 || n < 0 || row0 + n > cap) return fail(DPH_E_ARG, "dph_index_upload_rows: range");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpy(h->sh->db + row0 * DPH_DIM, host_rows, (size_t)n * DPH_DIM, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dst + row0 * DPH_DIM, host_rows, (size_t)n * DPH_DIM, hipMemcpyHostToDevice));
+    note_doc_rows(h->sh, row0, n);
     h->sh->finalized = false;
     return DPH_OK;
 }
 
 int dph_index_upload_rows_async(dph_index* h, int64_t row0, int64_t n, const int8_t* pinned_rows, void* stream) {
     DPH_NOT_TWINNED(h, "dph_index_upload_rows_async");
-    if (!h || !pinned_rows || row0 < 0 || n < 0 || row0 + n > h->sh->n_rows) return fail(DPH_E_ARG, "dph_index_upload_rows_async: range");
+    int64_t cap = 0;
+    int8_t* const dst = h ? upload_target(h->sh, &cap) : nullptr;
+    if (!h || !pinned_rows || row0 < 0 || n < 0 || row0 + n > cap) return fail(DPH_E_ARG, "dph_index_upload_rows_async: range");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->sh->db + row0 * DPH_DIM, pinned_rows, (size_t)n * DPH_DIM, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(dst + row0 * DPH_DIM, pinned_rows, (size_t)n * DPH_DIM, hipMemcpyHostToDevice, (hipStream_t)stream));
+    note_doc_rows(h->sh, row0, n);
     h->sh->finalized = false;
     return DPH_OK;
 }
@@ -342,6 +396,8 @@ int dph_index_set_f2o(dph_index* h, int64_t n_docs, const int32_t* doc_ids, cons
         HIPCHK(hipMemcpy(h->sh->f2o_off, &zero, 8, hipMemcpyHostToDevice));
     }
     h->sh->n_docs = n_docs;
+    h->sh->f2o_total = total;
+    if (h->sh->doc_rows) h->sh->finalized = false;      // the document rows are addressed through this table: finalize checks them against it
     return DPH_OK;
 }
 
@@ -443,6 +499,13 @@ int dph_index_finalize(dph_index* h, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     dph_shard* const s = h->sh;
     if (s->pq) {                         // a PQ index has no row statistics: its finalize builds the direct map
+        if (s->doc_rows) {
+            if (s->n_doc_rows != s->f2o_total)
+                return fail(DPH_E_STATE, "dph_index_finalize: " + std::to_string(s->n_doc_rows) + " document rows attached, the f2o table (dph_index_set_f2o) counts " +
+                                             std::to_string(s->f2o_total) + " words");
+            if (s->doc_rows_have.size() != 1 || s->doc_rows_have.begin()->first != 0 || s->doc_rows_have.begin()->second != s->n_doc_rows)
+                return fail(DPH_E_STATE, "dph_index_finalize: not every attached document row was uploaded (dph_index_upload_rows)");
+        }
         const int rc = dph_pq_finalize(s->pq, st);
         if (rc) return rc;
         s->finalized = true;
@@ -1702,6 +1765,13 @@ int dph_rescore_dev(dph_index* h, int direction, const float* qhalf_dev, int64_t
     if (!h->sh->doc_ids || !h->sh->f2o_off || !h->sh->f2o) return fail(DPH_E_STATE, "dph_rescore_dev: f2o metadata not set");
     if ((!doc_dev || !word_dev) && !h->sh->row2doc) return fail(DPH_E_STATE, "dph_rescore_dev: idx2id not set");
     HIPCHK(hipSetDevice(h->device));
+    if (h->sh->pq && h->sh->doc_rows) {  // the raw rows are resident: the HDF5 branch of the reference (index.py:246-273)
+        if (!h->sh->finalized) return fail(DPH_E_STATE, "dph_rescore_dev: call dph_index_finalize after attaching document rows");
+        const int rc = dph_pq_window_doc(h->sh->pq, direction, make_idmap(h->sh), h->sh->doc_rows, h->sh->n_doc_rows, h->sh->doc_lut, qhalf_dev, n_q, k, L, ids_dev,
+                                         doc_dev, word_dev, first_dev, h->sh->row2doc, h->sh->row2word, h->sh->doc_ids, h->sh->n_docs, h->sh->f2o_off, h->sh->f2o,
+                                         pred_word_dev, best_dev, argslot_dev, vecs_dev, (hipStream_t)stream);
+        return rc ? fail(rc, std::string("dph_rescore_dev: ") + dph_last_error()) : DPH_OK;
+    }
     if (h->sh->pq) {
         const int rc = dph_pq_window(h->sh->pq, direction, make_idmap(h->sh), qhalf_dev, n_q, k, L, ids_dev, doc_dev, word_dev, first_dev, h->sh->row2doc,
                                      h->sh->row2word, h->sh->doc_ids, h->sh->n_docs, h->sh->f2o_off, h->sh->f2o, pred_word_dev, best_dev, argslot_dev, vecs_dev,

@@ -526,3 +526,8 @@ int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf,
                   const int32_t* doc, const int32_t* word, const float* first, const int32_t* row2doc, const int32_t* row2word,
                   const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off, const int32_t* f2o, int32_t* pred_word,
                   double* best, int32_t* argslot, float* vecs, hipStream_t st);
+// ... over the raw int8 rows of whole documents instead of reconstructions (the reference's HDF5 branch, dph_index_attach_doc_rows)
+int dph_pq_window_doc(dph_pq* p, int direction, dph_idmap idmap, const int8_t* doc_rows, int64_t n_doc_rows, const float* lut, const float* qhalf,
+                      int64_t n_q, int k, int L, const int64_t* ids, const int32_t* doc, const int32_t* word, const float* first,
+                      const int32_t* row2doc, const int32_t* row2word, const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off,
+                      const int32_t* f2o, int32_t* pred_word, double* best, int32_t* argslot, float* vecs, hipStream_t st);

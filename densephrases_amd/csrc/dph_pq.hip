@@ -8,6 +8,7 @@
 //   score(code) = <x', c_list> + sum_m LUT[m][code[m]]        pq_adc_kernel            (fp32, summed SEQUENTIALLY in m like FAISS' scalar scan)
 //   top-k       = k largest, (score desc, id asc)             pq_adc_kernel + pq_final_kernel
 //   reconstruct = c_list + concat_m codeword[m][code[m]]      pq_reconstruct_kernel / pq_window_kernel
+//   windows over the dump's raw int8 rows (HDF5 branch)       pq_window_doc_kernel     (dph_index_attach_doc_rows)
 //
 // ADC scan.  Work = (query row, probed list) pairs from the coarse probe masks, taken from a work queue by workgroups of
 // 1024 threads.  A workgroup keeps the row's LUT in LDS (M x 256 fp32 = 96 KiB at OPQ96) and walks the list in segments of
@@ -809,6 +810,106 @@ __global__ __launch_bounds__(256) void pq_window_kernel(
         }
     }
 }
+// ---------------------------------------------------------------------------------------------- window re-score (index.py:246-273, HDF5 branch)
+// The same windows over the dump's RAW int8 rows (dph_index_attach_doc_rows): what the reference reads when meta_compressed.pkl is
+// absent.  One wavefront per candidate, 12 bytes of a row per lane, like dph_window_kernel -- but a slot's row is addressed by
+// (document of the candidate, word +- i), row = f2o_off[doc slot] + word in the doc-row store, and a word outside [0, len) of the
+// document is a zero vector (:265, :270 clip the range, :333-336 / :358-361 fill the rest of the np.zeros window).  No direct-map
+// search per slot: the only one left is the candidate's own, for `vecs`.  The dot is <A q, dequant(row)> like pq_window_kernel's,
+// with lut[n + 128] = fp32(n / scale + offset) rounded ONCE from float64 (int8_to_float, :158-162, on an int8 array gives float64;
+// the assignment into the fp32 window rounds it).  vecs [c,0,:] is the candidate's own row as RAW int8 values (:383, :388 take
+// groups_*[...] before any dequant), [c,1,:] the de-quantised arg-max row; pq_unrotate_kernel multiplies them by R once / twice.
+__global__ __launch_bounds__(256) void pq_window_doc_kernel(
+    int direction, const int8_t* __restrict__ rows, int64_t n_doc_rows, const float* __restrict__ lut, pq_store s, dph_idmap idmap,
+    const float* __restrict__ qrot, int64_t n_cand, int k, int L, const int64_t* __restrict__ ids, const int32_t* __restrict__ doc_in,
+    const int32_t* __restrict__ word_in, const float* __restrict__ first, const int32_t* __restrict__ row2doc,
+    const int32_t* __restrict__ row2word, const int32_t* __restrict__ doc_ids, int64_t n_docs, const int64_t* __restrict__ f2o_off,
+    const int32_t* __restrict__ f2o, int32_t* __restrict__ pred_word, double* __restrict__ best, int32_t* __restrict__ argslot,
+    float* __restrict__ vecs) {
+    __shared__ float lut_lds[256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    lut_lds[tid] = lut[tid];
+    __syncthreads();
+    const int64_t c = (int64_t)blockIdx.x * 4 + (tid >> 6);
+    if (c >= n_cand) return;
+    const int64_t id = ids[c];
+    int64_t lc = dph_local_of_id(idmap, id);          // idx2id is indexed by the LOCAL id, clipped like get_idxs (index.py:128-133)
+    if (lc < 0) {
+        const int64_t first_id = idmap.n_groups ? idmap.id_offsets[0] : idmap.id_base;
+        lc = id < first_id ? 0 : idmap.n_ids - 1;
+        if (lc < 0) lc = 0;
+    }
+    const int d = doc_in ? doc_in[c] : row2doc[lc];
+    const int w = word_in ? word_in[c] : row2word[lc];
+    int64_t lo = 0, hi = n_docs;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (doc_ids[mid] < d) lo = mid + 1; else hi = mid; }
+    const bool have_doc = d >= 0 && lo < n_docs && doc_ids[lo] == d;
+    const int64_t fbase = have_doc ? f2o_off[lo] : 0;
+    const int64_t flen = have_doc ? f2o_off[lo + 1] - fbase : 0;
+    const bool own_in = have_doc && w >= 0 && w < flen;            // a candidate outside its document has no window at all
+    float q[12];
+    const float* qp = qrot + (c / k) * DPH_DIM + lane * 12;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) q[j] = qp[j];
+    // the 12 codes of this lane of the row of word ww of the candidate's document; false = the zero vector
+    auto load = [&](int64_t ww, unsigned (&wv)[3]) -> bool {
+        const int64_t row = fbase + ww;
+        if (!own_in || ww < 0 || ww >= flen || row >= n_doc_rows) return false;
+        const unsigned* p = (const unsigned*)(rows + row * DPH_DIM + lane * 12);
+        wv[0] = p[0]; wv[1] = p[1]; wv[2] = p[2];
+        return true;
+    };
+    double best_s = 0.0;
+    int best_slot = -1, best_word = -1;
+    const float f0 = first[c];
+    for (int sl = 0; sl < L; ++sl) {
+        const int i = direction == 0 ? sl : (L - 1 - sl);
+        const int64_t ww = direction == 0 ? (int64_t)w + i : (int64_t)w - i;
+        bool valid = own_in && ww >= 0 && ww < flen;                                   // index.py:305-321
+        if (valid) {
+            const int64_t gap = direction == 0 ? (int64_t)f2o[fbase + ww] - (int64_t)f2o[fbase + w]
+                                               : (int64_t)f2o[fbase + w] - (int64_t)f2o[fbase + ww];
+            valid = gap >= 0 && gap <= L;
+        }
+        double dot = 0.0;
+        unsigned wv[3];
+        if (load(ww, wv)) {
+#pragma unroll
+            for (int dd = 0; dd < 3; ++dd)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    dot += (double)q[dd * 4 + b] * (double)lut_lds[(int)(int8_t)(wv[dd] >> (8 * b)) + 128];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+        }
+        const double sc = (double)(f0 + (float)dot) + (valid ? 0.0 : -1e9);       // fp32 + fp32, then the float64 mask (:343 / :368)
+        if (best_slot < 0 || sc > best_s) { best_s = sc; best_slot = sl; best_word = valid ? (int)ww : -1; }
+    }
+    if (lane == 0) { pred_word[c] = best_word; best[c] = best_s; argslot[c] = best_slot; }
+    if (vecs) {
+        // a candidate the DIRECT MAP does not hold (another rank's, FAISS' -1 padding) gives zero vectors: see pq_window_kernel
+        const bool mine = pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, id) >= 0;
+        const int bi = direction == 0 ? best_slot : (L - 1 - best_slot);
+        const int64_t wwv[2] = {(int64_t)w, direction == 0 ? (int64_t)w + bi : (int64_t)w - bi};
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            float* o = vecs + (c * 2 + t) * DPH_DIM + lane * 12;
+            unsigned wv[3];
+            if (mine && load(wwv[t], wv)) {
+#pragma unroll
+                for (int dd = 0; dd < 3; ++dd)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        const int code = (int)(int8_t)(wv[dd] >> (8 * b));
+                        o[dd * 4 + b] = t == 0 ? (float)code : lut_lds[code + 128];
+                    }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 12; ++j) o[j] = 0.f;
+            }
+        }
+    }
+}
 // out[v, :] = in[v, :] @ R, R = A [768,768] row-major (index.py:340 `end.matmul(self.R)`, :381-389 `.dot(self.R)`), float64
 // accumulation; `twice[v & 1]` vectors get it applied a second time (the reference's pred_*_vecs are taken from the already
 // un-rotated window tensor and then multiplied by R again, :345,370 then :381-389 -- replicated as is)
@@ -887,6 +988,8 @@ struct dph_pq {
     dph_profiler prof;
     dph_event_pairs prof_events;                           // around the launches of the coarse filter's dominant kernel
     dph_event_pairs enc_events;                            // around the four launches of every chunk of dph_pq_encode: transform, assign, re-decide, codes
+    dph_event_pairs win_events;                            // around the window kernel of every dph_pq_window / dph_pq_window_doc (the rotation and un-rotation launches outside)
+    bool prof_windows = false;                             // ... only when dph_profile_enable was given bit 1 (on = 3): a serving loop that profiles its scans re-scores thousands of windows nobody reads
     std::vector<float> h_A;
     dev_buf<uint8_t> codes; dev_buf<int64_t> ids, list_off;
     std::vector<int64_t> h_list_off;
@@ -975,6 +1078,7 @@ int dph_pq_profile(dph_pq* p, int on) {
     if (!p) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
     p->prof.on = on != 0;
+    p->prof_windows = (on & 2) != 0;
     if (on) HIPCHK(p->prof.warm(64));
     return DPH_OK;
 }
@@ -986,7 +1090,7 @@ int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches) {
 int dph_pq_profile_read_each(dph_pq* p, int which, double* ms_out, int cap, int* n_out) {
     if (!p || !n_out) return fail(DPH_E_ARG, "null");
     HIPCHK(hipSetDevice(p->device));
-    return p->prof.drain(which == 2 ? p->enc_events : p->prof_events, nullptr, n_out, ms_out, cap);
+    return p->prof.drain(which == 3 ? p->win_events : which == 2 ? p->enc_events : p->prof_events, nullptr, n_out, ms_out, cap);
 }
 
 void dph_pq_free(dph_pq* p) {
@@ -1389,6 +1493,17 @@ int dph_pq_reconstruct_dev(dph_pq* p, const int64_t* ids_dev, int64_t n, float* 
     return DPH_OK;
 }
 
+// qrot = A q (no bias) of the n_q query halves of a window pass: what both window kernels take their dots with
+static int pq_rotate_query_halves(dph_pq* p, const float* qhalf, int64_t n_q, hipStream_t st) {
+    if (n_q > p->qrot_rows) {
+        p->qrot_rows = 0;
+        HIPCHK(p->qrot.alloc((size_t)n_q * DPH_DIM));
+        p->qrot_rows = n_q;
+    }
+    pq_launch_transform(qhalf, p->At, n_q, nullptr, p->qrot, nullptr, nullptr, p->device, st);
+    return DPH_OK;
+}
+
 int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf, int64_t n_q, int k, int L, const int64_t* ids,
                   const int32_t* doc, const int32_t* word, const float* first, const int32_t* row2doc, const int32_t* row2word,
                   const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off, const int32_t* f2o, int32_t* pred_word,
@@ -1396,15 +1511,34 @@ int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf,
     if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ window: index not finalized");
     HIPCHK(hipSetDevice(p->device));
     if (n_q <= 0) return DPH_OK;
-    if (n_q > p->qrot_rows) {
-        p->qrot_rows = 0;
-        HIPCHK(p->qrot.alloc((size_t)n_q * DPH_DIM));
-        p->qrot_rows = n_q;
-    }
-    pq_launch_transform(qhalf, p->At, n_q, nullptr, p->qrot, nullptr, nullptr, p->device, st);
+    const int rc = pq_rotate_query_halves(p, qhalf, n_q, st);
+    if (rc) return rc;
     const int64_t n_cand = n_q * k;
-    hipLaunchKernelGGL(pq_window_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, pq_store_of(p), idmap, p->qrot, n_cand, k, L,
-                       ids, doc, word, first, row2doc, row2word, doc_ids, n_docs, f2o_off, f2o, pred_word, best, argslot, vecs);
+    p->prof.bracket(p->prof.on && p->prof_windows ? &p->win_events : nullptr, st, [&] {
+        hipLaunchKernelGGL(pq_window_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, pq_store_of(p), idmap, p->qrot, n_cand, k, L,
+                           ids, doc, word, first, row2doc, row2word, doc_ids, n_docs, f2o_off, f2o, pred_word, best, argslot, vecs);
+    });
+    if (vecs && p->A) hipLaunchKernelGGL(pq_unrotate_kernel, dim3((unsigned)(2 * n_cand)), dim3(256), 0, st, vecs, p->A, 2 * n_cand);
+    HIPCHK(hipGetLastError());
+    return DPH_OK;
+}
+
+// the same over the raw int8 rows of whole documents (doc_rows [n_doc_rows,768] in f2o-CSR order, lut = the single-rounding codec table)
+int dph_pq_window_doc(dph_pq* p, int direction, dph_idmap idmap, const int8_t* doc_rows, int64_t n_doc_rows, const float* lut, const float* qhalf,
+                      int64_t n_q, int k, int L, const int64_t* ids, const int32_t* doc, const int32_t* word, const float* first,
+                      const int32_t* row2doc, const int32_t* row2word, const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off,
+                      const int32_t* f2o, int32_t* pred_word, double* best, int32_t* argslot, float* vecs, hipStream_t st) {
+    if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ window: index not finalized");
+    if (!doc_rows || !lut) return fail(DPH_E_STATE, "PQ window: no document rows attached");
+    HIPCHK(hipSetDevice(p->device));
+    if (n_q <= 0) return DPH_OK;
+    const int rc = pq_rotate_query_halves(p, qhalf, n_q, st);
+    if (rc) return rc;
+    const int64_t n_cand = n_q * k;
+    p->prof.bracket(p->prof.on && p->prof_windows ? &p->win_events : nullptr, st, [&] {
+        hipLaunchKernelGGL(pq_window_doc_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, doc_rows, n_doc_rows, lut, pq_store_of(p),
+                           idmap, p->qrot, n_cand, k, L, ids, doc, word, first, row2doc, row2word, doc_ids, n_docs, f2o_off, f2o, pred_word, best, argslot, vecs);
+    });
     if (vecs && p->A) hipLaunchKernelGGL(pq_unrotate_kernel, dim3((unsigned)(2 * n_cand)), dim3(256), 0, st, vecs, p->A, 2 * n_cand);
     HIPCHK(hipGetLastError());
     return DPH_OK;

@@ -32,6 +32,32 @@ class DocMeta:
     start: Optional[np.ndarray] = None   # int8 [n_f, 768]; dropped after upload when not needed
 
 
+def iter_doc_blocks(doc_ids, off, read_doc_into, block: int, buffers=None) -> Iterator[Tuple[int, np.ndarray]]:
+    """(row0, int8 [n,768]) blocks over WHOLE documents in the order of an f2o CSR (``doc_ids`` ascending, ``off`` its offsets):
+    row0 = off of the block's first document, each block the longest run of documents of at most ``block`` rows (a longer
+    document goes alone).  ``read_doc_into(out, d)`` fills ``out`` with document d's full ``start`` dataset.  ``buffers``: int8
+    [>= block, 768] arrays (the loader's pinned staging memory); block t is written into buffers[t % len(buffers)] when the
+    consumer ASKS for it, so the consumer waits for that buffer's last upload before it calls next()."""
+    j, turn, n_docs = 0, 0, len(doc_ids)
+    while j < n_docs:
+        j1 = j + 1
+        while j1 < n_docs and int(off[j1 + 1]) - int(off[j]) <= block:
+            j1 += 1
+        n = int(off[j1]) - int(off[j])
+        if n > 0:
+            if buffers is not None and n <= buffers[turn % len(buffers)].shape[0]:
+                out = buffers[turn % len(buffers)][:n]
+            else:
+                out = np.empty((n, 768), np.int8)
+            for d in range(j, j1):
+                a, b = int(off[d]) - int(off[j]), int(off[d + 1]) - int(off[j])
+                if b > a:
+                    read_doc_into(out[a:b], int(doc_ids[d]))
+            yield int(off[j]), out
+            turn += 1
+        j = j1
+
+
 class DocStore:
     def __init__(self, docs: Sequence[DocMeta], rows: Optional[np.ndarray] = None,
                  row2doc: Optional[np.ndarray] = None, row2word: Optional[np.ndarray] = None,
@@ -81,6 +107,27 @@ class DocStore:
         np.cumsum(lens, out=off[1:])
         f2o = (np.concatenate([np.asarray(get(d)) for d in ids]).astype(np.int32) if len(ids) else np.zeros(0, np.int32))
         return ids, off, f2o
+
+    def iter_doc_row_blocks(self, lo: int = 0, hi: Optional[int] = None, block: int = 1 << 18,
+                            buffers=None) -> Iterator[Tuple[int, np.ndarray]]:
+        """The raw rows of WHOLE documents in f2o-CSR order (ascending doc id, the order ``f2o_csr(lo, hi)`` returns): every
+        document's full ``start`` dataset, len(start) == len(f2o_start) -- not the filtered subset the index's rows are.  What a
+        PQ handle keeps next to its codes for MIPS(window_rows="raw") (dph_index_attach_doc_rows).  Blocks as ``iter_doc_blocks``."""
+        ids, off, _ = self.f2o_csr(lo, hi)
+
+        def read(out, d):
+            m = self.docs[d]
+            start = m.start
+            if start is None:                                # dropped after upload: the index's rows, if they are the whole document
+                sel = np.nonzero(self.row2doc == d)[0]
+                if len(sel) != out.shape[0] or not np.array_equal(self.row2word[sel], np.arange(out.shape[0])):
+                    raise ValueError(f"document {d}: its `start` rows are gone and the index holds only a subset of them")
+                start = self.rows[sel]
+            if start.shape[0] != out.shape[0]:
+                raise ValueError(f"document {d}: {start.shape[0]} start rows, {out.shape[0]} f2o_start entries")
+            out[:] = start
+
+        return iter_doc_blocks(ids, off, read, block, buffers)
 
     def doc_meta(self, doc_idx: int) -> DocMeta:
         if doc_idx not in self.docs:

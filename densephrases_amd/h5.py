@@ -455,7 +455,9 @@ class ReferenceDump:
     def attach_row_cache(self, cache_dir: str, lo: int, hi: int, write: bool = True, rows: bool = True) -> bool:
         """Serve ``read_rows_into`` / ``f2o_csr`` of the stored rows [lo, hi) from the packed copy under ``cache_dir`` when a
         valid one exists (returns True); otherwise, with ``write``, record what the HDF5 reads of that range deliver so
-        that ``finish_row_cache`` can leave one behind.  ``rows`` = False: the f2o CSR only (a PQ index never reads the rows)."""
+        that ``finish_row_cache`` can leave one behind.  ``rows`` = False: the f2o CSR only -- what a PQ index attaches, also
+        with MIPS(window_rows="raw"): the document rows it keeps then (``iter_doc_row_blocks``) are whole documents in f2o-CSR
+        order, another order than this copy's stored rows, and are read from the HDF5 files every time."""
         self._cache = None
         if hi <= lo:
             return False
@@ -623,6 +625,23 @@ class ReferenceDump:
             yield s, out
             turn += 1
             r = max(r, r0) + 1
+
+    def iter_doc_row_blocks(self, lo: int = 0, hi: Optional[int] = None, block: int = 1 << 18, buffers=None):
+        """The raw rows of WHOLE documents whose index rows lie in [lo, hi), in f2o-CSR order (ascending doc id, the order
+        ``f2o_csr(lo, hi)`` returns): every document's full ``start`` dataset as the reference's HDF5 branch reads it
+        (index.py:263-272), len(start) == len(f2o_start) -- NOT the filtered subset ``_read_rows_hdf5`` gathers for an `_ftN`
+        index.  Blocks and ``buffers`` as ``dump.iter_doc_blocks``.  Never served from the packed row cache: that copy is in
+        stored-row order."""
+        from .dump import iter_doc_blocks
+        ids, off, _ = self.f2o_csr(lo, hi)
+
+        def read(out, d):
+            ds = self.docs._group(d).dataset("start")
+            if len(ds) != out.shape[0]:
+                raise ValueError(f"document {d}: {len(ds)} start rows, {out.shape[0]} f2o_start entries")
+            ds.read_into(out, start=0)
+
+        return iter_doc_blocks(ids, off, read, block, buffers)
 
     def f2o_of(self, d: int) -> np.ndarray:
         d = int(d)

@@ -11,6 +11,7 @@ There is no CPU path: the module imports ``densephrases_amd._lib`` which raises 
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 import re
@@ -80,7 +81,7 @@ class MIPS(object):
     def __init__(self, phrase_dump_dir, index_path, idx2id_path, cuda=False, logging_level=logging.INFO,
                  device: Optional[int] = None, _store=None, rank: Optional[int] = None, world: Optional[int] = None,
                  dist=None, ivf: Optional[dict] = None, cache_dir: Optional[str] = None, force_collectives: bool = False,
-                 pq: Optional[dict] = None):
+                 pq: Optional[dict] = None, window_rows: Optional[str] = None):
         """Same arguments as the reference (index.py:24).  ``cuda`` is accepted for compatibility; the search always
         runs on the GPU.  ``index_path`` names the reference's ``index.faiss``; no FAISS file is read -- the index
         *is* the int8 dump in idx2id row order (build_phrase_index.py:192-276).
@@ -103,6 +104,14 @@ class MIPS(object):
         released; from there on the object is what a finished ``index.faiss`` gives.  ``"save"`` also writes that file.
         Not together with ``ivf=`` or ``world > 1``.
 
+        ``window_rows`` (only with an OPQ + IVFPQ ``index_path``; ValueError together with a flat index, ``ivf=`` or ``pq=``) picks
+        which of the reference's two window re-scoring branches (index.py:68-76) answers:
+        None / "reconstructed" (default) -- the RAM branch (:276-302): windows of PQ reconstructions of the ids id +- i;
+        "raw" -- the HDF5 branch (:246-273): the dump's raw int8 rows of the candidate's document stay resident next to the codes
+        (768 B per dump row) and the windows are those rows, addressed by word, zero past the document's ends;
+        "reference" -- whichever the reference itself would take over these paths: "reconstructed" iff ``meta_compressed.pkl``
+        lies next to ``/phrase`` and 'PQ' is in ``index_path`` (:72), else "raw".
+
         ``cache_dir`` (default: the environment's ``DPH_DUMP_CACHE``, unset = off): the first load of a row range leaves a
         packed copy of its rows and f2o table there (h5.ReferenceDump.attach_row_cache); later starts of the same range
         over unchanged artefacts stream that copy instead of touching every document of the HDF5 dump."""
@@ -124,6 +133,12 @@ class MIPS(object):
             raise ValueError("MIPS: world > 1 needs a torch.distributed process group (or a `dist` object)")
         if pq is not None and (ivf is not None or self.world > 1):
             raise ValueError("MIPS(pq=...): not together with ivf= (the trained index brings its own lists) or world > 1 (sharded compression is not built)")
+        if window_rows not in (None, "reconstructed", "raw", "reference"):
+            raise ValueError(f'MIPS(window_rows={window_rows!r}): None, "reconstructed", "raw" or "reference"')
+        if window_rows is not None and (ivf is not None or pq is not None):
+            raise ValueError("MIPS(window_rows=...): only over an OPQ + IVFPQ index file, not together with ivf= or pq= "
+                             "(building an index and keeping the rows in one go is not built)")
+        self.window_rows = "reconstructed"
         if device is None:
             device = int(os.environ.get("LOCAL_RANK", "0")) if self.world > 1 else 0
         store = _store if _store is not None else load_dump_and_index(phrase_dump_dir, index_path, idx2id_path)
@@ -139,11 +154,13 @@ class MIPS(object):
                 raise ValueError("MIPS(pq=...) compresses the raw dump; this index file already holds codes")
             if not isinstance(parsed, faiss_io.FlatIndex):
                 # the reference's own index type: OPQ + IVFPQ codes resident in HBM instead of the raw int8 rows
-                self._init_pq(parsed, store, device, ivf)
+                self._init_pq(parsed, store, device, ivf, window_rows)
                 logger.info(f"index ntotal: {self.index.ntotal} | PQ codes resident on GPU {device} | load {time() - t0:.1f}s")
                 return
             # fine_quant 'none' (build_phrase_index.py:117-118): a flat fp32 index of the de-quantised dump rows -- the
             # resident int8 dump below IS that index
+        if window_rows is not None:
+            raise ValueError("MIPS(window_rows=...): only over an OPQ + IVFPQ index file; a flat index re-scores the dump's rows as it is")
         n = store.n_rows
         if pq is not None:
             self._build_pq(store, device, dict(pq))
@@ -181,12 +198,20 @@ class MIPS(object):
         logger.info(f"index ntotal: {self.index.ntotal} | rows [{lo}, {hi}) resident on GPU {device} "
                     f"(rank {self.rank}/{self.world}) | load {time() - t0:.1f}s")
 
-    def _init_pq(self, parsed, store, device: int, ivf):
+    def _reference_window_rows(self) -> str:
+        """what index.py:69-76 decides from the paths: the RAM branch needs meta_compressed.pkl AND 'PQ' in the index path"""
+        d = str(self.phrase_dump_dir)
+        pkl = os.path.join(d[:d.index("/phrase")], "meta_compressed.pkl") if "/phrase" in d else None
+        return "reconstructed" if pkl is not None and os.path.exists(pkl) and "PQ" in str(self.index_path) else "raw"
+
+    def _init_pq(self, parsed, store, device: int, ivf, window_rows: Optional[str] = None):
         """``index_path`` is a real FAISS file holding IndexPreTransform(OPQMatrix) -> IndexIVFPQ (build_phrase_index.py:
         108-116, what ``1048576_flat_OPQ96`` names): codes, codebooks, coarse centroids and the OPQ matrix go to HBM
         (csrc/dph_pq.hip); search = FAISS' IVFPQ search, windows over reconstructed vectors un-rotated by R (index.py:
         282-302, 340, 365).  The dump's metadata (idx2id, f2o, documents) is used as for a raw-dump shard; its int8 rows
-        are not read.  Range-sharded (world > 1) like the raw dump: north_star "(or PQ-compressed) phrase dump ... range-partitioned"."""
+        are not read -- unless ``window_rows`` resolves to "raw": then the full ``start`` rows of this rank's documents are streamed
+        into HBM next to the codes and the windows follow the reference's HDF5 branch (:246-273; dph_index_attach_doc_rows).
+        Range-sharded (world > 1) like the raw dump: north_star "(or PQ-compressed) phrase dump ... range-partitioned"."""
         if ivf is not None:
             raise ValueError("MIPS(ivf=...) builds lists over the raw dump; a FAISS index file brings its own")
         n = store.n_rows
@@ -207,7 +232,8 @@ class MIPS(object):
         self.shard = _lib.Shard.from_faiss_index(parsed, device=device, keep=keep)
         if self.shard.n_rows != hi - lo:
             raise ValueError(f"MIPS: the index holds {self.shard.n_rows} codes for the rows [{lo}, {hi}) of this rank")
-        self._finish_pq(store, lo, hi, n)
+        self.window_rows = self._reference_window_rows() if window_rows == "reference" else (window_rows or "reconstructed")
+        self._finish_pq(store, lo, hi, n, raw_rows=self.window_rows == "raw")
 
     def _build_pq(self, store, device: int, pq: dict):
         """``pq={"trained": ...}``: the dump's rows go to HBM like a flat shard, add_with_ids_resident turns them into the codes and
@@ -240,8 +266,10 @@ class MIPS(object):
             faiss_io.write_index(self.shard.to_faiss_index(trained), str(pq["save"]))
         self._finish_pq(store, 0, n, n)
 
-    def _finish_pq(self, store, lo: int, hi: int, n: int):
-        """what a PQ shard with its lists in place still needs: the dump's metadata, the direct map, the nprobe clamp, R"""
+    def _finish_pq(self, store, lo: int, hi: int, n: int, raw_rows: bool = False):
+        """what a PQ shard with its lists in place still needs: the dump's metadata, the direct map, the nprobe clamp, R -- and, with
+        ``raw_rows``, the raw rows of the documents of [lo, hi) in the order of the f2o table (a rank keeps the rows of its own
+        documents: the partition is document-aligned and a window never leaves its document)"""
         self.shard.set_idx2id(store.row2doc[lo:hi], store.row2word[lo:hi])
         groups = store.id_groups(lo, hi)
         if groups is None and self.world > 1:
@@ -250,9 +278,14 @@ class MIPS(object):
             self.shard.set_id_groups(*groups)
         if self._cache_dir is not None:
             store.attach_row_cache(self._cache_dir, lo, hi, rows=False)
-        self.shard.set_f2o(*store.f2o_csr(lo, hi))
+        csr = store.f2o_csr(lo, hi)
+        self.shard.set_f2o(*csr)
         if self._cache_dir is not None:
             store.finish_row_cache()
+        if raw_rows and int(csr[1][-1]) > 0:
+            self.shard.attach_doc_rows(int(csr[1][-1]))
+            self.shard.set_codec(store.offset, store.scale)
+            self._upload_doc_rows(store, lo, hi)
         self.shard.finalize()
         self.pq = dict(self.shard.pq)
         if self.pq["nprobe"] > self.pq["nlist"]:               # an index with fewer lists than the reference's nprobe = 256 (index.py:53)
@@ -290,21 +323,10 @@ class MIPS(object):
     def _upload(self, store, lo: int, hi: int, block_rows: int = 1 << 18):
         """rows [lo, hi) of the dump -> the shard.  Two pinned staging buffers of ``block_rows`` rows (192 MiB each): the
         HDF5 read of block t+1 overlaps the host->HBM copy of block t; host memory holds two blocks, not the dump."""
-        import ctypes as C
         import torch
         if hi <= lo:
             return
-        nbytes = block_rows * _lib.DIM
-        ptrs, views = [], []
-        for _ in range(2):
-            p = C.c_void_p()
-            _lib._chk(_lib.lib.dph_host_alloc_pinned(nbytes, C.byref(p)))
-            ptrs.append(p)
-            views.append(np.ctypeslib.as_array((C.c_int8 * nbytes).from_address(p.value)).reshape(block_rows, _lib.DIM))
-        dev = torch.device("cuda", self.shard.device)
-        stream = torch.cuda.Stream(device=dev)
-        events = [None, None]
-        try:
+        with self._staging(block_rows) as (ptrs, views, stream, events):
             turn, r0 = 0, lo
             starts = store.doc_starts()
             while r0 < hi:
@@ -334,6 +356,49 @@ class MIPS(object):
                 r0 = r1
                 turn += 1
             stream.synchronize()
+
+    def _upload_doc_rows(self, store, lo: int, hi: int, block_rows: int = 1 << 18):
+        """The full ``start`` rows of the documents of [lo, hi) -> the doc-row store of a PQ shard (Shard.attach_doc_rows), through
+        the same two pinned staging buffers: ``store.iter_doc_row_blocks`` fills buffer t & 1 when block t is asked for, so the
+        upload that last used it is waited for first."""
+        import torch
+        with self._staging(block_rows) as (ptrs, views, stream, events):
+            it = store.iter_doc_row_blocks(lo, hi, block=block_rows, buffers=views)
+            turn = 0
+            while True:
+                b = turn & 1
+                if events[b] is not None:
+                    events[b].synchronize()
+                nxt = next(it, None)
+                if nxt is None:
+                    break
+                r0, rows = nxt
+                if rows.shape[0] <= block_rows and rows.ctypes.data == ptrs[b].value:
+                    self.shard.upload_async(ptrs[b].value, r0, rows.shape[0], stream.cuda_stream)
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+                    events[b] = ev
+                else:                                   # a document longer than a staging buffer
+                    self.shard.upload(rows, r0)
+                turn += 1
+            stream.synchronize()
+
+    @contextlib.contextmanager
+    def _staging(self, block_rows: int):
+        """(pinned pointers, their int8 [block_rows, 768] views, an upload stream, [None, None] for the events) of the loader's two
+        staging buffers; freed on the way out"""
+        import ctypes as C
+        import torch
+        nbytes = block_rows * _lib.DIM
+        ptrs, views = [], []
+        try:
+            for _ in range(2):
+                p = C.c_void_p()
+                _lib._chk(_lib.lib.dph_host_alloc_pinned(nbytes, C.byref(p)))
+                ptrs.append(p)
+                views.append(np.ctypeslib.as_array((C.c_int8 * nbytes).from_address(p.value)).reshape(block_rows, _lib.DIM))
+            dev = torch.device("cuda", self.shard.device)
+            yield ptrs, views, torch.cuda.Stream(device=dev), [None, None]
         finally:
             for p in ptrs:
                 _lib.lib.dph_host_free_pinned(p)
@@ -347,8 +412,9 @@ class MIPS(object):
 
     @classmethod
     def from_store(cls, store: DocStore, device: int = 0, logging_level=logging.WARNING, ivf: Optional[dict] = None,
-                   pq: Optional[dict] = None):
-        return cls(None, "in-memory", None, logging_level=logging_level, device=device, _store=store, ivf=ivf, pq=pq)
+                   pq: Optional[dict] = None, window_rows: Optional[str] = None):
+        return cls(None, "in-memory", None, logging_level=logging_level, device=device, _store=store, ivf=ivf, pq=pq,
+                   window_rows=window_rows)
 
     @classmethod
     def from_shard(cls, shard: "_lib.Shard", store, logging_level=logging.WARNING):

@@ -200,12 +200,14 @@ def synthetic_pq_parts(n_codes: int, nlist: int, M: int = 96, seed: int = 0, ske
 
 
 def synthetic_pq_shard(n_codes: int, nlist: int, M: int = 96, device: int = 0, seed: int = 0, return_parts: bool = False,
-                       doc_len: int = 0, skew: str = "", hot: float = 0.18):
+                       doc_len: int = 0, skew: str = "", hot: float = 0.18, doc_rows: bool = False):
     """A PQ index resident in HBM for TIMING the IVFPQ search (csrc/dph_pq.hip) at full size: random 8-bit codes, random
     codebooks and coarse centroids, list lengths with exponential weights (or a ``skew``: see ``_pq_list_sizes`` / ``synthetic_pq_parts``), a
     Householder reflection x permutation as the OPQ matrix -- what the scan costs does not depend on what the codes mean (parity: tests/test_pq.py on trained indexes).
     ``doc_len`` > 0: idx2id / f2o of documents of ``doc_len`` consecutive ids with every token kept (what SynthDocStore describes), so
     that MIPS.search runs end to end over the index; 0: a single stand-in document (search only).
+    ``doc_rows`` (with ``doc_len``): raw int8 rows for every word of every document next to the codes (dph_index_attach_doc_rows;
+    one random block of 2^18 rows uploaded again and again from pinned memory) -- the windows then follow the reference's HDF5 branch.
     Returns (shard, A, centroids, list_sizes) (+ codebooks and the code block with ``return_parts``)."""
     import ctypes as C
     from . import _lib
@@ -230,6 +232,19 @@ def synthetic_pq_shard(n_codes: int, nlist: int, M: int = 96, device: int = 0, s
         s.set_f2o(np.arange(n_docs, dtype=np.int32), np.arange(0, (n_docs + 1) * doc_len, doc_len, dtype=np.int64),
                   np.tile(np.arange(doc_len, dtype=np.int32), n_docs))
         del ids
+        if doc_rows:
+            total, blk = n_docs * doc_len, 1 << 18
+            s.attach_doc_rows(total)
+            p = C.c_void_p()
+            _lib._chk(_lib.lib.dph_host_alloc_pinned(blk * 768, C.byref(p)))
+            try:
+                view = np.ctypeslib.as_array((C.c_int8 * (blk * 768)).from_address(p.value))
+                view[:] = np.random.default_rng(seed + 5).integers(-128, 128, blk * 768, dtype=np.int8)
+                for r0 in range(0, total, blk):
+                    s.upload_async(p.value, r0, min(blk, total - r0))
+                _lib._chk(_lib.lib.dph_stream_synchronize(int(device), None))
+            finally:
+                _lib.lib.dph_host_free_pinned(p)
     else:
         s.set_idx2id(np.zeros(n_codes, np.int32), np.zeros(n_codes, np.int32))
         s.set_f2o(np.zeros(1, np.int32), np.asarray([0, 1], np.int64), np.zeros(1, np.int32))

@@ -244,6 +244,28 @@ int dph_index_set_pq(dph_index* h, const float* A, const float* b, const float* 
 int dph_index_set_pq_list_sizes(dph_index* h, const int64_t* sizes);
 int dph_index_upload_pq_codes(dph_index* h, int64_t pos0, int64_t n, const uint8_t* codes, const int64_t* ids);
 int dph_index_get_transform(dph_index* h, float* A_out /* [768*768] */);
+/* ---- the HDF5 branch of the reference's window re-score on such an index (index.py:68-76, 246-273: taken whenever meta_compressed.pkl
+ * is absent or 'PQ' is not in the index path -- "Will read metadata directly from hdf5 files").  That branch re-scores the dump's RAW int8
+ * `start` rows, not reconstructions.  dph_index_attach_doc_rows allocates [n_doc_rows,768] int8 in HBM next to the codes of a PQ handle
+ * (before dph_index_finalize, once); dph_index_upload_rows(_async) then fill THAT store and dph_index_set_codec applies to it.  Layout:
+ * whole documents in the order of the f2o CSR (dph_index_set_f2o), row of (document slot d, word w) = f2o_off[d] + w, i.e. every
+ * document's full `start` dataset (len(start) == len(f2o_start)), also where the index's ids skip dump rows (_ftN filtered indexes).
+ * dph_index_finalize fails with DPH_E_STATE unless n_doc_rows == f2o_off[n_docs] and every row was uploaded.  From then on
+ * dph_rescore(_dev) on the handle follow the HDF5 branch (dph_search*, dph_reconstruct and dph_index_get_transform are untouched):
+ *   slot row   the row of (document of the candidate, word[c] +- i) -- not id +- i; a word outside [0, len) of the document is a ZERO
+ *              vector after de-quantisation (:265, :270 clip the range; :333-336 fill left-, :358-361 right-aligned into np.zeros); a
+ *              candidate whose own word lies outside its document, or whose document the handle does not know, has an all-zero window
+ *   dequant    fp32(n / scale + offset), the float64 value rounded once (:158-162 on an int8 array, assigned into the fp32 window at :334)
+ *   score      score[c,s] = (double)(first[c] + (float)dot) + (valid ? 0 : -1e9), dot = <A qhalf, dequant(row)> accumulated in float64 and
+ *              rounded once (= <qhalf, dequant(row) R>, :340-343); valid from the f2o CSR as ever; arg-max takes the first maximum;
+ *              pred_word = -1 when the winner is masked
+ *   vecs       [c,0,:] = the candidate's own row as RAW int8 values, not de-quantised, times R once (:383, :388 take groups_*[...] before
+ *              any dequant); [c,1,:] = dequant(arg-max row) times R TWICE (:345, :370, then :381-389)
+ *   ownership  a candidate whose id the direct map does not hold -- another rank's, or FAISS' -1 padding -- gives ZERO vectors.  For the
+ *              padding this DEVIATES from the reference, whose HDF5 branch would return the row of the clipped id (:133); such results
+ *              carry score <= -1e5 and never leave search_phrase (:420).
+ * Range-sharded: a rank attaches the rows of the documents of its own (document-aligned) range; windows never leave a document. */
+int dph_index_attach_doc_rows(dph_index* h, int64_t n_doc_rows);
 /* ---- filling such an index on the device: index.add_with_ids behind a TRAINED index (build_phrase_index.py:145-153; add_to_index,
  * :156-279, feeds it the dump rows; training itself -- :96-142 -- is not replaced).  The handle needs its parameters (dph_index_set_pq), no codes.
  *   dph_pq_encode_dev            replaces the encoding half of add_with_ids (:145-153).  x_dev [n,768] fp32 -> list_dev[n], codes_dev[n,M]:
@@ -287,7 +309,8 @@ int dph_id2docword(dph_index* h, const int64_t* I, int64_t n, int32_t* doc, int3
  * speaks).  A raw-dump shard holds the ids of its id map (id_base + row, or the id groups); a PQ shard holds the
  * ids of its direct map -- the ids uploaded with its codes, what dph_reconstruct answers -- whatever the id map
  * says (sparse or offset ids without id groups are held).  The idx2id lookup of a NULL doc / word goes through
- * the id map on both: the local id, clipped into [0, n_ids). */
+ * the id map on both: the local id, clipped into [0, n_ids).
+ * A PQ shard with document rows attached (dph_index_attach_doc_rows) re-scores the dump's raw rows instead: see there. */
 int dph_rescore(dph_index* h, int direction, const float* qhalf /*[n_q,768]*/, int64_t n_q, int k, int L,
                 const int64_t* ids, const int32_t* doc, const int32_t* word, const float* first,
                 int32_t* pred_word, double* best, int32_t* argslot, float* vecs);
