@@ -1144,6 +1144,19 @@ static dph_idmap make_idmap(const dph_shard* s) {
     return m;
 }
 
+// what a window re-score launch is asked for (dph_rescore_dev): the caller's arrays and the shard's idx2id / f2o metadata
+static dph_window_args make_window_args(const dph_index* h, int direction, const float* qhalf, int64_t n_q, int k, int L, const int64_t* ids,
+                                        const int32_t* doc, const int32_t* word, const float* first, int32_t* pred_word, double* best,
+                                        int32_t* argslot, float* vecs) {
+    const dph_shard* s = h->sh;
+    dph_window_args a{};
+    a.direction = direction; a.idmap = make_idmap(s); a.qhalf = qhalf; a.n_cand = n_q * k; a.k = k; a.L = L;
+    a.ids = ids; a.doc_in = doc; a.word_in = word; a.first = first;
+    a.row2doc = s->row2doc; a.row2word = s->row2word; a.doc_ids = s->doc_ids; a.n_docs = s->n_docs; a.f2o_off = s->f2o_off; a.f2o = s->f2o;
+    a.pred_word = pred_word; a.best = best; a.argslot = argslot; a.vecs = vecs;
+    return a;
+}
+
 static dph_pass make_pass(dph_index* h, const dph_scratch::qimg& q, const float* x, int q0, int n_q, int qb) {
     dph_pass p{};
     p.db = h->sh->db; p.n_rows = h->sh->n_rows; p.row_ids = h->sh->row_ids;
@@ -1765,22 +1778,16 @@ int dph_rescore_dev(dph_index* h, int direction, const float* qhalf_dev, int64_t
     if (!h->sh->doc_ids || !h->sh->f2o_off || !h->sh->f2o) return fail(DPH_E_STATE, "dph_rescore_dev: f2o metadata not set");
     if ((!doc_dev || !word_dev) && !h->sh->row2doc) return fail(DPH_E_STATE, "dph_rescore_dev: idx2id not set");
     HIPCHK(hipSetDevice(h->device));
-    if (h->sh->pq && h->sh->doc_rows) {  // the raw rows are resident: the HDF5 branch of the reference (index.py:246-273)
-        if (!h->sh->finalized) return fail(DPH_E_STATE, "dph_rescore_dev: call dph_index_finalize after attaching document rows");
-        const int rc = dph_pq_window_doc(h->sh->pq, direction, make_idmap(h->sh), h->sh->doc_rows, h->sh->n_doc_rows, h->sh->doc_lut, qhalf_dev, n_q, k, L, ids_dev,
-                                         doc_dev, word_dev, first_dev, h->sh->row2doc, h->sh->row2word, h->sh->doc_ids, h->sh->n_docs, h->sh->f2o_off, h->sh->f2o,
-                                         pred_word_dev, best_dev, argslot_dev, vecs_dev, (hipStream_t)stream);
+    const dph_shard* sh = h->sh;
+    const dph_window_args a = make_window_args(h, direction, qhalf_dev, n_q, k, L, ids_dev, doc_dev, word_dev, first_dev, pred_word_dev, best_dev,
+                                               argslot_dev, vecs_dev);
+    if (sh->pq) {
+        // the raw rows are resident: the HDF5 branch of the reference (index.py:246-273); otherwise windows of reconstructions
+        if (sh->doc_rows && !sh->finalized) return fail(DPH_E_STATE, "dph_rescore_dev: call dph_index_finalize after attaching document rows");
+        const int rc = dph_pq_window(sh->pq, a, sh->doc_rows, sh->n_doc_rows, sh->doc_lut, (hipStream_t)stream);
         return rc ? fail(rc, std::string("dph_rescore_dev: ") + dph_last_error()) : DPH_OK;
     }
-    if (h->sh->pq) {
-        const int rc = dph_pq_window(h->sh->pq, direction, make_idmap(h->sh), qhalf_dev, n_q, k, L, ids_dev, doc_dev, word_dev, first_dev, h->sh->row2doc,
-                                     h->sh->row2word, h->sh->doc_ids, h->sh->n_docs, h->sh->f2o_off, h->sh->f2o, pred_word_dev, best_dev, argslot_dev, vecs_dev,
-                                     (hipStream_t)stream);
-        return rc ? fail(rc, std::string("dph_rescore_dev: ") + dph_last_error()) : DPH_OK;
-    }
-    dph_launch_window(direction, h->sh->db, h->sh->n_rows, make_idmap(h->sh), h->sh->lut_dev, qhalf_dev, n_q * k, k, L, ids_dev, doc_dev,
-                      word_dev, first_dev, h->sh->row2doc, h->sh->row2word, h->sh->doc_ids, h->sh->n_docs, h->sh->f2o_off, h->sh->f2o, h->sh->inv_row,
-                      pred_word_dev, best_dev, argslot_dev, vecs_dev, (hipStream_t)stream);
+    dph_launch_window(a, nullptr, sh->db, sh->n_rows, sh->lut_dev, sh->inv_row, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return DPH_OK;
 }

@@ -240,6 +240,47 @@ __device__ __forceinline__ int64_t dph_local_of_id(const dph_idmap& m, int64_t i
     return r < m.row_starts[lo + 1] - m.row_starts[lo] ? m.row_starts[lo] + r : -1;
 }
 
+// ---- the stored OPQ + IVFPQ index as the reconstruct / window kernels read it (dph_pq.hip fills it, pq_store_of)
+struct pq_store {
+    const float* cent; const float* pqc; const uint8_t* codes; const int64_t* list_off; const int64_t* dm_ids; const unsigned* dm_pos;
+    int64_t ntotal; int nlist; int M; int dsub; int by_residual;
+};
+// the direct map: position of the code of `id` in the list-major store, -1 = not in the index
+__device__ __forceinline__ int64_t pq_pos_of_id(const int64_t* dm_ids, const unsigned* dm_pos, int64_t n, int64_t id) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (dm_ids[mid] < id) lo = mid + 1; else hi = mid; }
+    return (lo < n && dm_ids[lo] == id) ? (int64_t)dm_pos[lo] : -1;
+}
+__device__ __forceinline__ int pq_list_of_pos(const int64_t* list_off, int nlist, int64_t pos) {
+    int lo = 0, hi = nlist - 1;                                  // last list whose offset is <= pos and that is not empty there
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (list_off[mid] <= pos) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+// component j of the reconstruction of the code at `pos` (rotated space, fp32: decode, then one add of the centroid)
+__device__ __forceinline__ float pq_component(const pq_store& s, int64_t pos, int list, int j) {
+    const int m = j / s.dsub, t = j - m * s.dsub;
+    float v = s.pqc[((int64_t)m * 256 + s.codes[pos * s.M + m]) * s.dsub + t];
+    if (s.by_residual) v = __fadd_rn(v, s.cent[(int64_t)list * DPH_DIM + j]);
+    return v;
+}
+
+// ---- window re-score (dph_window.hip): what one launch is asked for, whatever serves the slot vectors.  Filled once per call by
+// dph_rescore_dev (make_window_args); n_cand = n_q * k candidates, query half c / k for candidate c.
+struct dph_window_args {
+    int direction;                                              // 0: slots id + i (end windows), 1: id - i (start windows)
+    dph_idmap idmap;
+    const float* qhalf;                                         // [n_cand / k, 768]
+    int64_t n_cand; int k; int L;
+    const int64_t* ids; const int32_t* doc_in; const int32_t* word_in; const float* first;     // [n_cand]; doc_in / word_in NULL: idx2id
+    const int32_t* row2doc; const int32_t* row2word;            // idx2id by local id
+    const int32_t* doc_ids; int64_t n_docs; const int64_t* f2o_off; const int32_t* f2o;        // the f2o CSR
+    int32_t* pred_word; double* best; int32_t* argslot; float* vecs;                           // [n_cand] x 3, [n_cand,2,768] or NULL
+};
+// The one launch.  pq = NULL: the raw int8 rows of a flat / grouped / list-major shard (rows [n_rows,768], lut, inv_row or NULL);
+// pq, rows = NULL: reconstructions of the PQ index; pq and rows: the doc-row store [n_rows,768] in f2o-CSR order with its lut.
+void dph_launch_window(const dph_window_args& a, const pq_store* pq, const int8_t* rows, int64_t n_rows, const float* lut,
+                       const int32_t* inv_row, hipStream_t st);
+
 // device-side gate of the retry launches: a kernel whose `gate` pointer is non-NULL serves rows
 // [gate_base, min(*gate, gate_base + rows of the pass)) and exits at once when that range is empty, so the retry chain
 // can be enqueued without a host round trip (it costs a few empty launches when every row certified).
@@ -471,12 +512,6 @@ void dph_launch_fill(int8_t* db, int64_t n_rows, int64_t id_base, uint64_t seed,
 void dph_launch_rownorm(const int8_t* db, int64_t n_rows, const int64_t* row_ids, const int* mu_dev, unsigned long long* max_out,
                         unsigned* hist, unsigned long long cut2, unsigned* out_rows, unsigned* out_count, unsigned out_cap,
                         hipStream_t st);
-void dph_launch_window(int direction, const int8_t* db, int64_t n_rows, dph_idmap idmap, const float* lut_dev,
-                       const float* qhalf, int64_t n_cand, int k, int L, const int64_t* ids, const int32_t* doc,
-                       const int32_t* word, const float* first, const int32_t* row2doc, const int32_t* row2word,
-                       const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off, const int32_t* f2o,
-                       const int32_t* inv_row, int32_t* pred_word, double* best, int32_t* argslot, float* vecs,
-                       hipStream_t st);
 void dph_launch_merge(const float* D_parts, const int64_t* I_parts, const double* best_parts, const int32_t* pred_parts,
                       const int32_t* status_parts, const double* bound_parts, int n_parts, int64_t stride_bytes, int64_t n,
                       int k, float* D_out, int64_t* I_out, int32_t* src_out, double* best_out, int32_t* pred_out,
@@ -522,12 +557,6 @@ int dph_pq_profile_read(dph_pq* p, double* ms_total, int* launches);
 int dph_pq_profile_read_each(dph_pq* p, int which, double* ms_out, int cap, int* n_out);
 int dph_pq_search_dev(dph_pq* p, const float* x_dev, int64_t n, int k, int nprobe, float* D, int64_t* I, int32_t* status, hipStream_t st);
 int dph_pq_reconstruct_dev(dph_pq* p, const int64_t* ids_dev, int64_t n, float* out_dev, int32_t* found_dev, hipStream_t st);
-int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf, int64_t n_q, int k, int L, const int64_t* ids,
-                  const int32_t* doc, const int32_t* word, const float* first, const int32_t* row2doc, const int32_t* row2word,
-                  const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off, const int32_t* f2o, int32_t* pred_word,
-                  double* best, int32_t* argslot, float* vecs, hipStream_t st);
-// ... over the raw int8 rows of whole documents instead of reconstructions (the reference's HDF5 branch, dph_index_attach_doc_rows)
-int dph_pq_window_doc(dph_pq* p, int direction, dph_idmap idmap, const int8_t* doc_rows, int64_t n_doc_rows, const float* lut, const float* qhalf,
-                      int64_t n_q, int k, int L, const int64_t* ids, const int32_t* doc, const int32_t* word, const float* first,
-                      const int32_t* row2doc, const int32_t* row2word, const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off,
-                      const int32_t* f2o, int32_t* pred_word, double* best, int32_t* argslot, float* vecs, hipStream_t st);
+// window re-score of a PQ shard: doc_rows = NULL re-scores reconstructions, otherwise the raw int8 rows of whole documents (the
+// reference's HDF5 branch, dph_index_attach_doc_rows; doc_lut = the single-rounding codec table).  a.qhalf is rotated here.
+int dph_pq_window(dph_pq* p, dph_window_args a, const int8_t* doc_rows, int64_t n_doc_rows, const float* doc_lut, hipStream_t st);

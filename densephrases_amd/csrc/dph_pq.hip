@@ -7,8 +7,8 @@
 //   LUT[m][j]   = <x'_m, codeword[m][j]>                      pq_lut_kernel            (float64 accumulation, one rounding)
 //   score(code) = <x', c_list> + sum_m LUT[m][code[m]]        pq_adc_kernel            (fp32, summed SEQUENTIALLY in m like FAISS' scalar scan)
 //   top-k       = k largest, (score desc, id asc)             pq_adc_kernel + pq_final_kernel
-//   reconstruct = c_list + concat_m codeword[m][code[m]]      pq_reconstruct_kernel / pq_window_kernel
-//   windows over the dump's raw int8 rows (HDF5 branch)       pq_window_doc_kernel     (dph_index_attach_doc_rows)
+//   reconstruct = c_list + concat_m codeword[m][code[m]]      pq_reconstruct_kernel / window_kernel<PqCodes> (dph_window.hip)
+//   windows over the dump's raw int8 rows (HDF5 branch)       window_kernel<DocRows>   (dph_index_attach_doc_rows)
 //
 // ADC scan.  Work = (query row, probed list) pairs from the coarse probe masks, taken from a work queue by workgroups of
 // 1024 threads.  A workgroup keeps the row's LUT in LDS (M x 256 fp32 = 96 KiB at OPQ96) and walks the list in segments of
@@ -688,27 +688,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_final_kernel(const uint2* __res
 }
 
 // ---------------------------------------------------------------------------------------------- direct map, reconstruct
-__device__ __forceinline__ int64_t pq_pos_of_id(const int64_t* dm_ids, const unsigned* dm_pos, int64_t n, int64_t id) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (dm_ids[mid] < id) lo = mid + 1; else hi = mid; }
-    return (lo < n && dm_ids[lo] == id) ? (int64_t)dm_pos[lo] : -1;
-}
-__device__ __forceinline__ int pq_list_of_pos(const int64_t* list_off, int nlist, int64_t pos) {
-    int lo = 0, hi = nlist - 1;                                  // last list whose offset is <= pos and that is not empty there
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (list_off[mid] <= pos) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-struct pq_store {
-    const float* cent; const float* pqc; const uint8_t* codes; const int64_t* list_off; const int64_t* dm_ids; const unsigned* dm_pos;
-    int64_t ntotal; int nlist; int M; int dsub; int by_residual;
-};
-// component j of the reconstruction of the code at `pos` (rotated space, fp32: decode, then one add of the centroid)
-__device__ __forceinline__ float pq_component(const pq_store& s, int64_t pos, int list, int j) {
-    const int m = j / s.dsub, t = j - m * s.dsub;
-    float v = s.pqc[((int64_t)m * 256 + s.codes[pos * s.M + m]) * s.dsub + t];
-    if (s.by_residual) v = __fadd_rn(v, s.cent[(int64_t)list * DPH_DIM + j]);
-    return v;
-}
+// (pq_store, pq_pos_of_id, pq_list_of_pos, pq_component: dph_internal.h, shared with the window kernel of dph_window.hip)
 __global__ __launch_bounds__(256) void pq_reconstruct_kernel(pq_store s, const int64_t* __restrict__ ids, int64_t n,
                                                              float* __restrict__ out, int32_t* __restrict__ found) {
     const int64_t c = blockIdx.x;
@@ -718,198 +698,7 @@ __global__ __launch_bounds__(256) void pq_reconstruct_kernel(pq_store s, const i
     for (int j = threadIdx.x; j < DPH_DIM; j += 256) out[c * DPH_DIM + j] = pos >= 0 ? pq_component(s, pos, list, j) : 0.f;
 }
 
-// ---------------------------------------------------------------------------------------------- window re-score (index.py:276-370, PQ branch)
-// One wavefront per candidate, like dph_window_kernel, over RECONSTRUCTED vectors: slot row = reconstruct(id +- i) in the
-// rotated space, zero when the id is unknown (index.py:285-288); the reference un-rotates it (`end.matmul(self.R)`, :340)
-// and takes the fp32 dot with the query half -- <q, v' R> = <R q, v'> = <A q, v'>, so the dot is taken with the ROTATED
-// query half qrot = A q (pq_transform_kernel without the bias) in float64 and rounded once, no un-rotation of 2*B*k*L vectors.
-__global__ __launch_bounds__(256) void pq_window_kernel(
-    int direction, pq_store s, dph_idmap idmap, const float* __restrict__ qrot, int64_t n_cand, int k, int L,
-    const int64_t* __restrict__ ids, const int32_t* __restrict__ doc_in, const int32_t* __restrict__ word_in,
-    const float* __restrict__ first, const int32_t* __restrict__ row2doc, const int32_t* __restrict__ row2word,
-    const int32_t* __restrict__ doc_ids, int64_t n_docs, const int64_t* __restrict__ f2o_off, const int32_t* __restrict__ f2o,
-    int32_t* __restrict__ pred_word, double* __restrict__ best, int32_t* __restrict__ argslot, float* __restrict__ vecs) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t c = (int64_t)blockIdx.x * 4 + (tid >> 6);
-    if (c >= n_cand) return;
-    const int64_t id = ids[c];
-    int64_t lc = dph_local_of_id(idmap, id);          // idx2id is indexed by the LOCAL id (ownership is the direct map's, see `vecs` below)
-    if (lc < 0) {
-        const int64_t first_id = idmap.n_groups ? idmap.id_offsets[0] : idmap.id_base;
-        lc = id < first_id ? 0 : idmap.n_ids - 1;
-        if (lc < 0) lc = 0;
-    }
-    const int d = doc_in ? doc_in[c] : row2doc[lc];
-    const int w = word_in ? word_in[c] : row2word[lc];
-    int64_t lo = 0, hi = n_docs;
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (doc_ids[mid] < d) lo = mid + 1; else hi = mid; }
-    const bool have_doc = d >= 0 && lo < n_docs && doc_ids[lo] == d;
-    const int64_t fbase = have_doc ? f2o_off[lo] : 0;
-    const int64_t flen = have_doc ? f2o_off[lo + 1] - fbase : 0;
-    float q[12];
-    const float* qp = qrot + (c / k) * DPH_DIM + lane * 12;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) q[j] = qp[j];
-    double best_s = 0.0;
-    int best_slot = -1, best_word = -1;
-    const float f0 = first[c];
-    // Where the window's codes lie: lane sl resolves slot sl -- the binary search of its id in the direct map (28 dependent loads at
-    // 170 M codes) and of its position in the list offsets (20) -- for up to 64 slots AT ONCE; round 4 walked the slots one after the
-    // other, 2 * B * k * L searches in series per wave: 127 us per direction at B = 64, k = 10, L = 10 (profiles/r05_kernel_trace_pq_e2e_b64.csv)
-    int64_t my_pos = -1;
-    int my_list = 0;
-    for (int sl = 0; sl < L; ++sl) {
-        if ((sl & 63) == 0) {
-            const int mine_sl = sl + lane;
-            my_pos = -1;
-            my_list = 0;
-            if (mine_sl < L) {
-                const int i = direction == 0 ? mine_sl : (L - 1 - mine_sl);
-                my_pos = pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, direction == 0 ? id + i : id - i);
-                if (my_pos >= 0) my_list = pq_list_of_pos(s.list_off, s.nlist, my_pos);
-            }
-        }
-        const int i = direction == 0 ? sl : (L - 1 - sl);
-        const int64_t ww = direction == 0 ? (int64_t)w + i : (int64_t)w - i;
-        const int64_t pos = __shfl(my_pos, sl & 63);
-        const int list = __shfl(my_list, sl & 63);
-        bool valid = have_doc && w >= 0 && w < flen && ww >= 0 && ww < flen;
-        if (valid) {
-            const int64_t gap = direction == 0 ? (int64_t)f2o[fbase + ww] - (int64_t)f2o[fbase + w]
-                                               : (int64_t)f2o[fbase + w] - (int64_t)f2o[fbase + ww];
-            valid = gap >= 0 && gap <= L;
-        }
-        double dot = 0.0;
-        if (pos >= 0) {
-#pragma unroll
-            for (int j = 0; j < 12; ++j) dot += (double)q[j] * (double)pq_component(s, pos, list, lane * 12 + j);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
-        }
-        const double sc = (double)(f0 + (float)dot) + (valid ? 0.0 : -1e9);       // fp32 + fp32, then the float64 mask (:343 / :368)
-        if (best_slot < 0 || sc > best_s) { best_s = sc; best_slot = sl; best_word = valid ? (int)ww : -1; }
-    }
-    if (lane == 0) { pred_word[c] = best_word; best[c] = best_s; argslot[c] = best_slot; }
-    if (vecs) {
-        // rotated-space vectors for now: [c,0,:] the candidate's own, [c,1,:] the arg-max slot's; pq_unrotate_kernel finishes them
-        const int bi = direction == 0 ? best_slot : (L - 1 - best_slot);
-        const int64_t idv[2] = {id, direction == 0 ? id + bi : id - bi};
-        // The shard holds a candidate when its DIRECT MAP does (what dph_reconstruct answers), whatever the id map says: ids of a PQ
-        // shard without id groups are sparse or offset (n_ids = ntotal, id_base = 0), and dph_local_of_id knows none of them.
-        // A candidate this shard does not hold contributes ZERO vectors, also for a window slot that happens to lie in this shard's
-        // range (the first rows of the next rank's range): the ranks' vectors are SUMMED (index.py _window_vectors), exactly one
-        // rank -- the candidate's, the only one that uploaded its code -- may speak
-        const int64_t own_pos = pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, id);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int64_t pos = t == 0 ? own_pos : (own_pos >= 0 ? pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, idv[t]) : -1);
-            const int list = pos >= 0 ? pq_list_of_pos(s.list_off, s.nlist, pos) : 0;
-            float* o = vecs + (c * 2 + t) * DPH_DIM + lane * 12;
-#pragma unroll
-            for (int j = 0; j < 12; ++j) o[j] = pos >= 0 ? pq_component(s, pos, list, lane * 12 + j) : 0.f;
-        }
-    }
-}
-// ---------------------------------------------------------------------------------------------- window re-score (index.py:246-273, HDF5 branch)
-// The same windows over the dump's RAW int8 rows (dph_index_attach_doc_rows): what the reference reads when meta_compressed.pkl is
-// absent.  One wavefront per candidate, 12 bytes of a row per lane, like dph_window_kernel -- but a slot's row is addressed by
-// (document of the candidate, word +- i), row = f2o_off[doc slot] + word in the doc-row store, and a word outside [0, len) of the
-// document is a zero vector (:265, :270 clip the range, :333-336 / :358-361 fill the rest of the np.zeros window).  No direct-map
-// search per slot: the only one left is the candidate's own, for `vecs`.  The dot is <A q, dequant(row)> like pq_window_kernel's,
-// with lut[n + 128] = fp32(n / scale + offset) rounded ONCE from float64 (int8_to_float, :158-162, on an int8 array gives float64;
-// the assignment into the fp32 window rounds it).  vecs [c,0,:] is the candidate's own row as RAW int8 values (:383, :388 take
-// groups_*[...] before any dequant), [c,1,:] the de-quantised arg-max row; pq_unrotate_kernel multiplies them by R once / twice.
-__global__ __launch_bounds__(256) void pq_window_doc_kernel(
-    int direction, const int8_t* __restrict__ rows, int64_t n_doc_rows, const float* __restrict__ lut, pq_store s, dph_idmap idmap,
-    const float* __restrict__ qrot, int64_t n_cand, int k, int L, const int64_t* __restrict__ ids, const int32_t* __restrict__ doc_in,
-    const int32_t* __restrict__ word_in, const float* __restrict__ first, const int32_t* __restrict__ row2doc,
-    const int32_t* __restrict__ row2word, const int32_t* __restrict__ doc_ids, int64_t n_docs, const int64_t* __restrict__ f2o_off,
-    const int32_t* __restrict__ f2o, int32_t* __restrict__ pred_word, double* __restrict__ best, int32_t* __restrict__ argslot,
-    float* __restrict__ vecs) {
-    __shared__ float lut_lds[256];
-    const int tid = threadIdx.x, lane = tid & 63;
-    lut_lds[tid] = lut[tid];
-    __syncthreads();
-    const int64_t c = (int64_t)blockIdx.x * 4 + (tid >> 6);
-    if (c >= n_cand) return;
-    const int64_t id = ids[c];
-    int64_t lc = dph_local_of_id(idmap, id);          // idx2id is indexed by the LOCAL id, clipped like get_idxs (index.py:128-133)
-    if (lc < 0) {
-        const int64_t first_id = idmap.n_groups ? idmap.id_offsets[0] : idmap.id_base;
-        lc = id < first_id ? 0 : idmap.n_ids - 1;
-        if (lc < 0) lc = 0;
-    }
-    const int d = doc_in ? doc_in[c] : row2doc[lc];
-    const int w = word_in ? word_in[c] : row2word[lc];
-    int64_t lo = 0, hi = n_docs;
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (doc_ids[mid] < d) lo = mid + 1; else hi = mid; }
-    const bool have_doc = d >= 0 && lo < n_docs && doc_ids[lo] == d;
-    const int64_t fbase = have_doc ? f2o_off[lo] : 0;
-    const int64_t flen = have_doc ? f2o_off[lo + 1] - fbase : 0;
-    const bool own_in = have_doc && w >= 0 && w < flen;            // a candidate outside its document has no window at all
-    float q[12];
-    const float* qp = qrot + (c / k) * DPH_DIM + lane * 12;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) q[j] = qp[j];
-    // the 12 codes of this lane of the row of word ww of the candidate's document; false = the zero vector
-    auto load = [&](int64_t ww, unsigned (&wv)[3]) -> bool {
-        const int64_t row = fbase + ww;
-        if (!own_in || ww < 0 || ww >= flen || row >= n_doc_rows) return false;
-        const unsigned* p = (const unsigned*)(rows + row * DPH_DIM + lane * 12);
-        wv[0] = p[0]; wv[1] = p[1]; wv[2] = p[2];
-        return true;
-    };
-    double best_s = 0.0;
-    int best_slot = -1, best_word = -1;
-    const float f0 = first[c];
-    for (int sl = 0; sl < L; ++sl) {
-        const int i = direction == 0 ? sl : (L - 1 - sl);
-        const int64_t ww = direction == 0 ? (int64_t)w + i : (int64_t)w - i;
-        bool valid = own_in && ww >= 0 && ww < flen;                                   // index.py:305-321
-        if (valid) {
-            const int64_t gap = direction == 0 ? (int64_t)f2o[fbase + ww] - (int64_t)f2o[fbase + w]
-                                               : (int64_t)f2o[fbase + w] - (int64_t)f2o[fbase + ww];
-            valid = gap >= 0 && gap <= L;
-        }
-        double dot = 0.0;
-        unsigned wv[3];
-        if (load(ww, wv)) {
-#pragma unroll
-            for (int dd = 0; dd < 3; ++dd)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    dot += (double)q[dd * 4 + b] * (double)lut_lds[(int)(int8_t)(wv[dd] >> (8 * b)) + 128];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
-        }
-        const double sc = (double)(f0 + (float)dot) + (valid ? 0.0 : -1e9);       // fp32 + fp32, then the float64 mask (:343 / :368)
-        if (best_slot < 0 || sc > best_s) { best_s = sc; best_slot = sl; best_word = valid ? (int)ww : -1; }
-    }
-    if (lane == 0) { pred_word[c] = best_word; best[c] = best_s; argslot[c] = best_slot; }
-    if (vecs) {
-        // a candidate the DIRECT MAP does not hold (another rank's, FAISS' -1 padding) gives zero vectors: see pq_window_kernel
-        const bool mine = pq_pos_of_id(s.dm_ids, s.dm_pos, s.ntotal, id) >= 0;
-        const int bi = direction == 0 ? best_slot : (L - 1 - best_slot);
-        const int64_t wwv[2] = {(int64_t)w, direction == 0 ? (int64_t)w + bi : (int64_t)w - bi};
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            float* o = vecs + (c * 2 + t) * DPH_DIM + lane * 12;
-            unsigned wv[3];
-            if (mine && load(wwv[t], wv)) {
-#pragma unroll
-                for (int dd = 0; dd < 3; ++dd)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        const int code = (int)(int8_t)(wv[dd] >> (8 * b));
-                        o[dd * 4 + b] = t == 0 ? (float)code : lut_lds[code + 128];
-                    }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 12; ++j) o[j] = 0.f;
-            }
-        }
-    }
-}
+// ---------------------------------------------------------------------------------------------- window re-score: dph_window.hip (PqCodes, DocRows)
 // out[v, :] = in[v, :] @ R, R = A [768,768] row-major (index.py:340 `end.matmul(self.R)`, :381-389 `.dot(self.R)`), float64
 // accumulation; `twice[v & 1]` vectors get it applied a second time (the reference's pred_*_vecs are taken from the already
 // un-rotated window tensor and then multiplied by R again, :345,370 then :381-389 -- replicated as is)
@@ -988,7 +777,7 @@ struct dph_pq {
     dph_profiler prof;
     dph_event_pairs prof_events;                           // around the launches of the coarse filter's dominant kernel
     dph_event_pairs enc_events;                            // around the four launches of every chunk of dph_pq_encode: transform, assign, re-decide, codes
-    dph_event_pairs win_events;                            // around the window kernel of every dph_pq_window / dph_pq_window_doc (the rotation and un-rotation launches outside)
+    dph_event_pairs win_events;                            // around the window kernel of every dph_pq_window (the rotation and un-rotation launches outside)
     bool prof_windows = false;                             // ... only when dph_profile_enable was given bit 1 (on = 3): a serving loop that profiles its scans re-scores thousands of windows nobody reads
     std::vector<float> h_A;
     dev_buf<uint8_t> codes; dev_buf<int64_t> ids, list_off;
@@ -1493,7 +1282,7 @@ int dph_pq_reconstruct_dev(dph_pq* p, const int64_t* ids_dev, int64_t n, float* 
     return DPH_OK;
 }
 
-// qrot = A q (no bias) of the n_q query halves of a window pass: what both window kernels take their dots with
+// qrot = A q (no bias) of the n_q query halves of a window pass: what both PQ row sources take their dots with
 static int pq_rotate_query_halves(dph_pq* p, const float* qhalf, int64_t n_q, hipStream_t st) {
     if (n_q > p->qrot_rows) {
         p->qrot_rows = 0;
@@ -1504,42 +1293,20 @@ static int pq_rotate_query_halves(dph_pq* p, const float* qhalf, int64_t n_q, hi
     return DPH_OK;
 }
 
-int dph_pq_window(dph_pq* p, int direction, dph_idmap idmap, const float* qhalf, int64_t n_q, int k, int L, const int64_t* ids,
-                  const int32_t* doc, const int32_t* word, const float* first, const int32_t* row2doc, const int32_t* row2word,
-                  const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off, const int32_t* f2o, int32_t* pred_word,
-                  double* best, int32_t* argslot, float* vecs, hipStream_t st) {
+// doc_rows = NULL: windows of reconstructions; otherwise over the raw int8 rows of whole documents (doc_rows [n_doc_rows,768] in
+// f2o-CSR order, doc_lut = the single-rounding codec table)
+int dph_pq_window(dph_pq* p, dph_window_args a, const int8_t* doc_rows, int64_t n_doc_rows, const float* doc_lut, hipStream_t st) {
     if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ window: index not finalized");
+    if (doc_rows && !doc_lut) return fail(DPH_E_STATE, "PQ window: no document rows attached");
     HIPCHK(hipSetDevice(p->device));
-    if (n_q <= 0) return DPH_OK;
-    const int rc = pq_rotate_query_halves(p, qhalf, n_q, st);
+    if (a.n_cand <= 0) return DPH_OK;
+    const int rc = pq_rotate_query_halves(p, a.qhalf, a.n_cand / a.k, st);
     if (rc) return rc;
-    const int64_t n_cand = n_q * k;
-    p->prof.bracket(p->prof.on && p->prof_windows ? &p->win_events : nullptr, st, [&] {
-        hipLaunchKernelGGL(pq_window_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, pq_store_of(p), idmap, p->qrot, n_cand, k, L,
-                           ids, doc, word, first, row2doc, row2word, doc_ids, n_docs, f2o_off, f2o, pred_word, best, argslot, vecs);
-    });
-    if (vecs && p->A) hipLaunchKernelGGL(pq_unrotate_kernel, dim3((unsigned)(2 * n_cand)), dim3(256), 0, st, vecs, p->A, 2 * n_cand);
-    HIPCHK(hipGetLastError());
-    return DPH_OK;
-}
-
-// the same over the raw int8 rows of whole documents (doc_rows [n_doc_rows,768] in f2o-CSR order, lut = the single-rounding codec table)
-int dph_pq_window_doc(dph_pq* p, int direction, dph_idmap idmap, const int8_t* doc_rows, int64_t n_doc_rows, const float* lut, const float* qhalf,
-                      int64_t n_q, int k, int L, const int64_t* ids, const int32_t* doc, const int32_t* word, const float* first,
-                      const int32_t* row2doc, const int32_t* row2word, const int32_t* doc_ids, int64_t n_docs, const int64_t* f2o_off,
-                      const int32_t* f2o, int32_t* pred_word, double* best, int32_t* argslot, float* vecs, hipStream_t st) {
-    if (!p || !p->finalized) return fail(DPH_E_STATE, "PQ window: index not finalized");
-    if (!doc_rows || !lut) return fail(DPH_E_STATE, "PQ window: no document rows attached");
-    HIPCHK(hipSetDevice(p->device));
-    if (n_q <= 0) return DPH_OK;
-    const int rc = pq_rotate_query_halves(p, qhalf, n_q, st);
-    if (rc) return rc;
-    const int64_t n_cand = n_q * k;
-    p->prof.bracket(p->prof.on && p->prof_windows ? &p->win_events : nullptr, st, [&] {
-        hipLaunchKernelGGL(pq_window_doc_kernel, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, st, direction, doc_rows, n_doc_rows, lut, pq_store_of(p),
-                           idmap, p->qrot, n_cand, k, L, ids, doc, word, first, row2doc, row2word, doc_ids, n_docs, f2o_off, f2o, pred_word, best, argslot, vecs);
-    });
-    if (vecs && p->A) hipLaunchKernelGGL(pq_unrotate_kernel, dim3((unsigned)(2 * n_cand)), dim3(256), 0, st, vecs, p->A, 2 * n_cand);
+    a.qhalf = p->qrot;
+    const pq_store store = pq_store_of(p);
+    p->prof.bracket(p->prof.on && p->prof_windows ? &p->win_events : nullptr, st,
+                    [&] { dph_launch_window(a, &store, doc_rows, n_doc_rows, doc_lut, nullptr, st); });
+    if (a.vecs && p->A) hipLaunchKernelGGL(pq_unrotate_kernel, dim3((unsigned)(2 * a.n_cand)), dim3(256), 0, st, a.vecs, p->A, 2 * a.n_cand);
     HIPCHK(hipGetLastError());
     return DPH_OK;
 }

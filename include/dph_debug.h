@@ -87,7 +87,7 @@ int dph_profile_read_all(dph_index* h, double* scan_ms_total, int* scan_launches
 /* Every bracketed launch since the last read on its own, in launch order: ms_out[0 .. min(*n_out, cap)) (which = 0: the full scans -- on a
  * PQ index the coarse filter scans, each launch alone inside its pair --, 1: the ladder levels' scans; 2, PQ index only: the launches of dph_pq_encode_dev -- transform, list estimate, list
  * re-decision, codes, in that order for every chunk of 65536 rows; 3, PQ index only: the window kernel of every dph_rescore(_dev) --
- * pq_window_kernel, or pq_window_doc_kernel on a handle with document rows; bracketed only after dph_profile_enable(h, 3)).  What `rocprofv3 --kernel-trace`
+ * window_kernel<PqCodes>, or window_kernel<DocRows> on a handle with document rows; bracketed only after dph_profile_enable(h, 3)).  What `rocprofv3 --kernel-trace`
  * reports per dispatch of the same kernel: bench.py --trace_out writes both side by side. */
 int dph_profile_read_each(dph_index* h, int which, double* ms_out, int cap, int* n_out);
 

@@ -24,9 +24,10 @@ GROUP_OFFSETS = [0, 10 ** 9, 3 * 10 ** 9]
 GROUP_ROWS = [0, 200, 350, 700]                   # unequal sizes 200 / 150 / 350
 N_LISTS, EMPTY_LIST = 7, 3
 
-# (n_q, k), L: every L with a partial last workgroup (n_q * k not a multiple of 4), every shape with L = 10
+# (n_q, k), L: every L with a partial last workgroup (n_q * k not a multiple of 4), every shape with L = 10; L = 65 passes the
+# staging point of the window kernel at every 64th slot
 RAW_SHAPES = [((1, 1), 1), ((1, 1), 10), ((1, 3), 2), ((1, 3), 10), ((1, 3), 33), ((3, 4), 10), ((5, 7), 1), ((5, 7), 10),
-              ((5, 7), 20), ((5, 7), 33), ((64, 10), 10), ((64, 10), 33)]
+              ((5, 7), 20), ((5, 7), 33), ((5, 7), 65), ((64, 10), 10), ((64, 10), 33)]
 L_ALL = (1, 2, 10, 20, 33)
 
 

@@ -1,5 +1,5 @@
-"""dph_rescore called directly: dph_window_kernel (flat, grouped, list-major and range-split raw-dump shards) and
-pq_window_kernel + pq_unrotate_kernel (OPQ + IVFPQ shards) against the float64 restatement of tests/_window_ref.py, by its
+"""dph_rescore called directly: window_kernel<FlatRows> (flat, grouped, list-major and range-split raw-dump shards) and
+window_kernel<PqCodes> + pq_unrotate_kernel (OPQ + IVFPQ shards) against the float64 restatement of tests/_window_ref.py, by its
 acceptance rule: arg-max and pred_word exact wherever the restatement decides them (it must for 99 % of every input set:
 tests/test_window_ref.py asserts that without a GPU), `best` within the tolerance the documented roundings allow, flat
 vectors bit for bit, un-rotated PQ vectors within one fp32 rounding per product.  The input sets are tests/_window_sets.py."""
@@ -93,7 +93,7 @@ def _hold(name, b, out, vec_of, held, A=None):
 # ------------------------------------------------------------------------------------------------- raw-dump shards
 @DIRECTIONS
 def test_flat_shard_every_shape_with_the_candidate_edges_mixed_in(direction):
-    """(n_q, k) from one candidate to 640, L 1 .. 33, partial last workgroups; ids -1, around both ends of the shard and
+    """(n_q, k) from one candidate to 640, L 1 .. 65, partial last workgroups; ids -1, around both ends of the shard and
     2^40, words and documents around every edge of the CSR, FAISS padding, (doc, word) that are not the id's, planted
     runs of identical rows (the first of them must win), saturated rows"""
     vec_of, held = S.flat_lookup()

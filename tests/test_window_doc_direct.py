@@ -1,5 +1,5 @@
 """dph_rescore / dph_rescore_dev called directly on PQ handles with the dump's raw rows attached (dph_index_attach_doc_rows):
-pq_window_doc_kernel + pq_unrotate_kernel against the float64 restatement of tests/_window_doc_ref.py, by the acceptance rule
+window_kernel<DocRows> + pq_unrotate_kernel against the float64 restatement of tests/_window_doc_ref.py, by the acceptance rule
 of tests/_window_ref.py -- arg-max and pred_word exact wherever the restatement decides them (99 % of every input set:
 tests/test_window_doc_ref.py asserts that without a GPU), `best` and the rotated vectors within the tolerance the documented
 roundings allow.  The input sets are tests/_window_doc_sets.py: document lengths 0, 1, 2, L - 1, L, L + 1 and ~70, f2o gaps
@@ -130,7 +130,7 @@ def test_own_vector_is_the_raw_int8_row_times_R_and_the_other_one_is_rotated_twi
 
 @DIRECTIONS
 def test_control_the_reconstruction_windows_of_a_handle_without_rows_answer_differently(direction):
-    """Same index, same inputs, R != I: the handle WITHOUT rows re-scores reconstructions of ids id +- i (pq_window_kernel), the one
+    """Same index, same inputs, R != I: the handle WITHOUT rows re-scores reconstructions of ids id +- i (window_kernel<PqCodes>), the one
     with rows the dump's raw rows of word +- i -- `best` must differ, or these tests would pass on either path."""
     v = S.variant("house")
     L = 10

@@ -70,7 +70,7 @@ def test_restatement_decides_every_candidate_of_the_pq_input_sets(variant):
     v = S.pq_variant(variant)
     late = 0
     for name, b, r in _share(S.pq_sets(variant), A=v.A):
-        if b.L > 64:            # arg-max slots that only the second 64-slot position lookup of pq_window_kernel serves
+        if b.L > 64:            # arg-max slots that only the second 64-slot position lookup of window_kernel<PqCodes> serves
             late += int((r.argslot >= 64).sum())
     assert late > 0
     if variant == "m48_sparse":

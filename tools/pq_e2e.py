@@ -2,7 +2,7 @@
 """The reference's shipping configuration end to end, alone (for a kernel trace): the synthetic OPQ96 / 2^20-list / 170 M-code index
 with idx2id + f2o (synth.synthetic_pq_shard, doc_len 100), then bench.pq_e2e -- MIPS.search, MIPS.search_stream and the GPU half alone.
     python tools/pq_e2e.py [--codes N] [--nlist L] > gpurun_out/r05_pq_e2e.json
-    rocprofv3 --kernel-trace --stats -d gpurun_out/prof_pq_e2e -- python tools/pq_e2e.py   (per-kernel microseconds incl. pq_window_kernel)"""
+    rocprofv3 --kernel-trace --stats -d out/prof_pq_e2e -- python tools/pq_e2e.py   (per-kernel microseconds incl. window_kernel<PqCodes>)"""
 import argparse
 import json
 import os

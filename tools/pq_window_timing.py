@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Per-launch time of the two window kernels of a PQ index at full size: pq_window_kernel (windows of reconstructions, the
-reference's RAM branch) on a handle without rows, and pq_window_doc_kernel (the dump's raw int8 rows, the HDF5 branch) on a
+"""Per-launch time of the two window kernels of a PQ index at full size: window_kernel<PqCodes> (windows of reconstructions, the
+reference's RAM branch) on a handle without rows, and window_kernel<DocRows> (the dump's raw int8 rows, the HDF5 branch) on a
 handle with the rows of every document attached -- the same synthetic 170 M-code index of tools/pq_timing.py, documents of
 100 words, B = 64, k = 10, L = 10, both directions, launches interleaved, read from the PQ profiler's event pairs
-(dph_profile_read_each, which = 3).  Timing only (parity: tests/test_window_doc_direct.py).  Prints one JSON line."""
+(dph_profile_read_each, which = 3).  The JSON keys keep the labels the two instantiations had as kernels of their own,
+"pq_window_kernel" and "pq_window_doc_kernel", so that earlier records compare.  Timing only (parity: tests/test_window_doc_direct.py).  Prints one JSON line."""
 import argparse
 import json
 import os
