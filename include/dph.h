@@ -138,11 +138,19 @@ void*   dph_index_rows_dev(dph_index* h);
  * exact scans until every row is certified exact.  It returns DPH_E_UNCERTIFIED in one case: a row has more exact
  * ties at its k-th place than the fp64 scan's hit buffer holds (2^20 per row); dph_search_stats.uncertified counts
  * such rows and D / I must not be used.  Neither form ever answers such a row with success.
+ * OPQ + IVFPQ indexes (dph_index_create_pq; dph_search and dph_search_ivf alike): the ADC scan keeps a bounded candidate list per
+ * query row -- sized from k, nprobe and the list lengths, every segment's share plus 512 -- and the final selection sorts at most 4096
+ * candidates (k + the ties at the k-th place).  Tie blocks of a few hundred equal scores are answered exactly, in id order.  A row
+ * whose ties at the k-th place exceed either buffer -- thousands of byte-identical codes in one probed list, or an all-zero query
+ * row on an index without a bias, for which every probed code scores 0.0 -- is NOT retried: the device form gives that row status
+ * DPH_ROW_UNCERTIFIED and every other row of the batch its exact answer with status 0; the host form returns DPH_E_UNCERTIFIED for
+ * the whole call ("candidate buffers of the PQ scan overflowed"), dph_search_stats.uncertified counts such rows and D / I must
+ * not be used.
  * NON-FINITE query rows (a NaN / Inf element; index.py:195-200 hands FAISS whatever the encoder produced): FAISS' flat search
  * answers such a row with ids -1 / scores -FLT_MAX (no score compares greater than its heap's threshold) and the other rows as
  * ever.  Same here, on every index type: that row gets I = -1, D = -FLT_MAX, status DPH_ROW_NONFINITE (device forms) and is counted
  * in dph_search_stats.nonfinite; the call returns DPH_OK and the row costs what an ordinary row costs.  Finite rows of any
- * magnitude (1e30, all zeros) are searched exactly. */
+ * magnitude (1e30, all zeros) are searched exactly (the all-zero row on a PQ index without a bias: the tie rule above). */
 int dph_search(dph_index* h, const float* x, int64_t n, int k, float* D, int64_t* I);
 /* device-pointer form, asynchronous on `stream`, no host round trip: the first attempt, then -- gated by a
  * device-side count, a few empty launches when nothing failed -- a retry scan of the uncertified rows under a bound

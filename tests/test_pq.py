@@ -14,7 +14,7 @@ import pytest
 from densephrases_amd import faiss_io as F
 from oracle import ivfpq_oracle as P
 from tests._golden import GOLD, compare_results, load_toy_docs
-from tests._pq_build import _random_index, _shard  # noqa: F401  (other test files import them from here)
+from tests._pq_build import _index_from_list_numbers, _random_index, _shard  # noqa: F401  (other test files import them from here)
 
 PY39 = "/opt/conda/bin/python3.9"
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -426,25 +426,6 @@ def test_pq_row_major_units_of_many_segments_take_their_bound_from_a_sample():
         _same_topk(D, I, Dr, Ir)
         assert s.stats()["uncertified"] == 0
     s.close()
-
-
-def _index_from_list_numbers(rng, nlist, M, lists, cent, ids=None):
-    """an IndexPreTransform(OPQ) -> IndexIVFPQ whose code i (random bytes) lies in list lists[i]"""
-    n = len(lists)
-    pqc = rng.normal(0, 0.1, (M, 256, 768 // M)).astype(np.float32)
-    codes = rng.integers(0, 256, (n, M), dtype=np.uint8)
-    order = np.argsort(lists, kind="stable")
-    ids = np.arange(n, dtype=np.int64) if ids is None else ids
-    list_codes = [np.zeros((0, M), np.uint8)] * nlist
-    list_ids = [np.zeros(0, np.int64)] * nlist
-    ls, cs, is_ = lists[order], codes[order], ids[order]
-    cuts = np.nonzero(np.diff(ls))[0] + 1
-    for seg_l, seg_c, seg_i in zip(np.split(ls, cuts), np.split(cs, cuts), np.split(is_, cuts)):
-        if len(seg_l):
-            list_codes[int(seg_l[0])], list_ids[int(seg_l[0])] = seg_c, seg_i
-    A = P.random_rotation(768, rng)
-    ix = F.PreTransformIndex([F.LinearTransform(A)], F.IVFPQIndex(768, nlist, M, 8, cent, pqc, list_codes, list_ids, True, 0, 1, 2), 768, True)
-    return ix, A
 
 
 @pytest.mark.gpu
