@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "dph_internal.h"
+#include "dph_plan.h"
 
 static thread_local std::string g_err;
 // (a HIP call that failed leaves its code as the thread's "last error" until somebody reads it: rocPRIM checks hipGetLastError() after its
@@ -404,81 +405,20 @@ int dph_index_set_f2o(dph_index* h, int64_t n_docs, const int32_t* doc_ids, cons
 // ---- shard statistics: what the bounds of the search are made of ------------------------------------------------------
 // Every bound (the low-digit bound of the filter, the score bound of the rows that were not re-scored) is a Cauchy-Schwarz
 // bound around the per-dimension mean code mu of the stored rows.  dph_index_finalize measures, in three passes over the rows:
-//   1. per-dimension sums -> mu_j (rounded mean), spread sd_j;
-//   2. the squared centred norms || n - mu ||^2: maximum, histogram -> median, and the outlier cut: ONE extreme row (a saturated
-//      code vector) would loosen a shard-wide bound for every query, so the DPH_OUTLIER_MAX largest-norm rows are taken out of it when
-//      that tightens it by more than 10 %: "outlier rows", scored exactly against every query (dph_outlier_kernel), never bounded;
-//   3. whether the rows are ALIKE.  They are not when (a) some dimensions sit far from the others for every row -- "rogue"
-//      dimensions: | mu_j - median mu | beyond 3.5 spreads of a typical dimension; a query of the same encoder carries them too and they
-//      would eat the range of its high digit -- or (b) the norms are heavy-tailed (largest non-outlier norm > 1.3 x the median): then
-//      the shard gets AUX ROWS (dph_scan.hip "the aux k-step") and the filter bounds every row by its own norm.
-static void choose_aux_layout(dph_shard* s) {
-    dph_aux_layout lay{};
-    lay.q2max = 64;
-    // (a shard the select step sorts whole is scanned cold -- no bound, nothing for aux rows to tighten -- and its handful of rows says
-    // little about dimensions)
-    if (s->n_rows <= 0 || s->aux_mode == 0 || (s->n_rows <= DPH_POOL_MAX && s->aux_mode < 0)) { s->aux_lay = lay; return; }
-    // rogue dimensions: mean far outside the spread the typical dimension has around the typical mean
-    std::vector<double> sds(s->sd_host, s->sd_host + DPH_DIM), mus(DPH_DIM);
-    for (int j = 0; j < DPH_DIM; ++j) mus[j] = (double)s->mu_host[j];
-    std::nth_element(sds.begin(), sds.begin() + DPH_DIM / 2, sds.end());
-    std::nth_element(mus.begin(), mus.begin() + DPH_DIM / 2, mus.end());
-    const double sd_med = std::max(1.0, sds[DPH_DIM / 2]), mu_med = mus[DPH_DIM / 2];
-    std::vector<std::pair<double, int>> rogue;          // (ratio, dimension): how many times the bulk's range a query needs there
-    for (int j = 0; j < DPH_DIM; ++j) {
-        const double ratio = fabs((double)s->mu_host[j] - mu_med) / (3.5 * sd_med);
-        if (ratio >= 1.2) rogue.push_back({ratio, j});
-    }
-    std::sort(rogue.begin(), rogue.end(), [](const std::pair<double, int>& x, const std::pair<double, int>& y) {
-        return x.first > y.first || (x.first == y.first && x.second < y.second); });
-    if (rogue.size() > 12) rogue.resize(12);            // at least two replica slots each
-    const bool heavy = s->rmed > 0.0 && s->rmax_cut > 1.3 * s->rmed;
-    // replica slots a query that looks like a row needs: its digit in a rogue dimension is `ratio` times the bulk's range.  Twelve fit the
-    // 16-byte aux row (4 norm slots), twenty-four the 32-byte one (8 norm slots); with fewer than it needs a query only loses a little
-    // resolution in its bulk (the scale is max_j |q_j| / (1 + R_j)), so the narrow row -- half the extra HBM bytes -- is taken when it suffices
-    int need = 0;
-    for (auto& r : rogue) need += std::max(1, (int)ceil(r.first) - 1);
-    int stride = s->aux_mode > 0 ? s->aux_mode : (!rogue.empty() ? (need <= 12 ? 16 : 32) : (heavy ? 4 : 0));
-    if (stride >= 16 && rogue.empty()) stride = 4;
-    if (stride == 0) { s->aux_lay = lay; return; }
-    lay.stride = stride;
-    lay.n_norm = stride == 32 ? 8 : 4;
-    if (stride >= 16) {
-        // the replica slots are dealt out in proportion to the ratios (largest remainder), every rogue dimension >= 1
-        const int n_slots = stride == 32 ? DPH_AUX_REP_MAX : 12;
-        double total = 0;
-        for (auto& r : rogue) total += r.first;
-        std::vector<int> cnt(rogue.size(), 1);
-        int left = n_slots - (int)rogue.size();
-        std::vector<double> want(rogue.size());
-        for (size_t i = 0; i < rogue.size(); ++i) want[i] = rogue[i].first / total * n_slots;
-        while (left > 0) {
-            size_t best = 0; double gap = -1e300;
-            for (size_t i = 0; i < rogue.size(); ++i) if (want[i] - cnt[i] > gap) { gap = want[i] - cnt[i]; best = i; }
-            cnt[best]++; left--;
-        }
-        int sl = 0;
-        for (size_t i = 0; i < rogue.size(); ++i)
-            for (int c = 0; c < cnt[i]; ++c) lay.rep_dim[sl++] = (short)rogue[i].second;
-        lay.n_rep = sl;
-    }
-    s->aux_lay = lay;
+//   1. per-dimension sums -> mu_j (rounded mean), spread sd_j (plan_col_stats);
+//   2. the squared centred norms || n - mu ||^2: maximum, histogram -> median, and the outlier cut (plan_norm_stats): ONE extreme row (a
+//      saturated code vector) would loosen a shard-wide bound for every query, so the DPH_OUTLIER_MAX largest-norm rows are taken out of
+//      it when that tightens it by more than 10 %: "outlier rows", scored exactly against every query (dph_outlier_kernel), never bounded;
+//   3. whether the rows are ALIKE (choose_aux_layout); a shard whose rows are not gets AUX ROWS (dph_scan.hip "the aux k-step").
+// The rules themselves stand in dph_plan.h; here the shard's state goes in and the plan comes back.
+static plan_aux_facts aux_facts(const dph_shard* s) {
+    return plan_aux_facts{s->n_rows, s->aux_mode, s->mu_host, s->sd_host, s->rmed, s->rmax_cut, s->rmax_all, s->n_out_found};
 }
-
-// norm unit and low-digit clamp of a layout on THIS shard: the norm codes of a row sum to ceil(norm / unit) <= 127 n_norm, and the
-// digit they meet, ceil(unit ||q2|| / 128), must fit int8: q2max <= 126 * 128 / (unit * sqrt(768))
-static void derive_aux_units(dph_shard* s) {
-    // outlier rows serve the shard-wide norm bound; with aux rows every row is bounded by its own norm and none is set aside
-    if (s->aux_lay.stride <= 0) { s->norm_unit = 1; s->n_out = s->n_out_found; s->rmax = s->n_out_found > 0 ? s->rmax_cut : s->rmax_all; return; }
-    s->n_out = 0;
-    s->rmax = s->rmax_all;
-    const double cap = 127.0 * s->aux_lay.n_norm;
-    int unit = (int)ceil(s->rmax_all / cap);
-    s->norm_unit = unit < 1 ? 1 : unit;
-    if (!s->aux_lay_forced) {
-        const int q2 = (int)floor(126.0 * 128.0 / ((double)s->norm_unit * 27.7129));
-        s->aux_lay.q2max = q2 > 64 ? 64 : (q2 < 1 ? 1 : q2);
-    }
+static void set_aux_plan(dph_shard* s, const plan_aux& a) {
+    s->aux_lay = a.lay; s->aux_lay_forced = a.forced; s->norm_unit = a.norm_unit; s->n_out = a.n_out; s->rmax = a.rmax;
+}
+static plan_list_facts list_facts(const dph_shard* s) {
+    return plan_list_facts{s->n_rows, s->n_tiles, s->nlist, s->lists_contiguous, s->max_list_tiles, s->total_segs};
 }
 
 static int build_aux_rows(dph_shard* s, hipStream_t st) {
@@ -518,13 +458,7 @@ int dph_index_finalize(dph_index* h, void* stream) {
     if (s->n_rows > 0) dph_launch_colstats(s->db, s->n_rows, s->row_ids, s->colsum_dev, st);
     HIPCHK(hipMemcpyAsync(sums.data(), s->colsum_dev, 2 * DPH_DIM * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int j = 0; j < DPH_DIM; ++j) {
-        const double mean = n_real > 0 ? (double)sums[j] / (double)n_real : 0.0;
-        const double var = n_real > 0 ? (double)sums[DPH_DIM + j] / (double)n_real - mean * mean : 0.0;
-        int m = (int)lrint(mean);
-        s->mu_host[j] = m < -128 ? -128 : (m > 127 ? 127 : m);
-        s->sd_host[j] = var > 0.0 ? sqrt(var) : 0.0;
-    }
+    plan_col_stats(sums.data(), n_real, s->mu_host, s->sd_host);
     HIPCHK(hipMemcpyAsync(s->mu_dev, s->mu_host, DPH_DIM * sizeof(int), hipMemcpyHostToDevice, st));
     // ---- 2. centred row norms
     HIPCHK(hipMemsetAsync(s->norm_dev, 0, 2 * sizeof(unsigned long long), st));
@@ -540,25 +474,10 @@ int dph_index_finalize(dph_index* h, void* stream) {
     s->rmax_cut = s->rmax_all;
     s->n_out = 0;
     s->n_out_found = 0;
-    {
-        uint64_t total = 0, run = 0;
-        for (int b = 0; b < DPH_NORM_BINS; ++b) total += hist[b];
-        s->rmed = 0.0;
-        for (int b = 0; b < DPH_NORM_BINS && total > 0; ++b) {
-            run += hist[b];
-            if (2 * run >= total) { s->rmed = sqrt(((double)b + 0.5) * DPH_NORM_BIN_W); break; }
-        }
-    }
-    // the lowest bin edge with at most DPH_OUTLIER_MAX rows above it
-    uint64_t above = 0;
-    int cut_bin = DPH_NORM_BINS;         // rows in bins >= cut_bin are outliers
-    for (int b = DPH_NORM_BINS - 1; b >= 0; --b) {
-        if (above + hist[b] > (uint64_t)DPH_OUTLIER_MAX) break;
-        above += hist[b];
-        cut_bin = b;
-    }
-    const unsigned long long cut2 = (unsigned long long)cut_bin * DPH_NORM_BIN_W;       // norm^2 < cut2 for the rest
-    if (above > 0 && cut_bin > 0 && (double)cut2 * 1.21 < (double)m) {
+    const plan_norms nrm = plan_norm_stats(hist.data(), m);
+    s->rmed = nrm.rmed;
+    const unsigned long long cut2 = nrm.cut2;
+    if (nrm.take_cut) {
         unsigned* cnt = (unsigned*)(s->norm_dev + 1);
         dph_launch_rownorm(s->db, s->n_rows, s->row_ids, s->mu_dev, nullptr, nullptr, cut2 - 1, s->outliers, cnt, DPH_OUTLIER_MAX, st);
         unsigned n_out = 0;
@@ -573,21 +492,8 @@ int dph_index_finalize(dph_index* h, void* stream) {
             s->rmax_cut = sqrt((double)cut2);
         }
     }
-    // ---- 3. aux rows
-    if (!s->aux_lay_forced) choose_aux_layout(s);
-    derive_aux_units(s);
-    if (s->aux_lay_forced && s->aux_lay.stride > 0) {
-        // a layout forced by dph_index_set_aux_layout survives a re-finalize only while its low-digit clamp still serves THESE rows
-        // (new rows with larger norms -> a larger norm unit -> the query's norm digit would not fit int8 and the per-row bound would be
-        // too small: wrong rows filtered, result still "certified").  Otherwise the shard chooses afresh and the ranks of a sharded job
-        // agree again (densephrases_amd: Shard.finalize resets the sync mark).
-        const int q2 = (int)floor(126.0 * 128.0 / ((double)s->norm_unit * 27.7129));
-        if (s->aux_lay.q2max > q2) {
-            s->aux_lay_forced = false;
-            choose_aux_layout(s);
-            derive_aux_units(s);
-        }
-    }
+    // ---- 3. aux rows: the layout is chosen unless a forced one still serves these rows (plan_aux_rows)
+    set_aux_plan(s, plan_aux_rows(aux_facts(s), s->aux_lay, s->aux_lay_forced));
     const int rc = build_aux_rows(s, st);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(st));
@@ -605,15 +511,10 @@ int dph_index_get_aux_layout(dph_index* h, int32_t* out) {
     if (!h || !out) return fail(DPH_E_ARG, "dph_index_get_aux_layout: null");
     if (!h->sh->finalized) return fail(DPH_E_STATE, "dph_index_get_aux_layout: call dph_index_finalize first");
     const dph_shard* src = h->sh;
-    out[0] = src->aux_lay.stride; out[1] = src->aux_lay.n_norm; out[2] = src->aux_lay.n_rep; out[3] = src->aux_lay.q2max;
-    if (src->aux_lay.stride <= 0) {
-        // no aux rows here, but another rank of the job may force some on this shard: report the clamp THIS shard's row norms would allow
-        // with the fewest norm slots a layout has (4), so that the minimum over the ranks is one every rank can set
-        const int unit = std::max(1, (int)ceil(src->rmax_all / (127.0 * 4.0)));
-        const int q2 = (int)floor(126.0 * 128.0 / ((double)unit * 27.7129));
-        out[3] = q2 > 64 ? 64 : (q2 < 1 ? 1 : q2);
-    }
-    for (int i = 0; i < DPH_AUX_REP_MAX; ++i) out[4 + i] = i < src->aux_lay.n_rep ? src->aux_lay.rep_dim[i] : -1;
+    plan_pack_layout(src->aux_lay, out);
+    // no aux rows here, but another rank of the job may force some on this shard: report the clamp THIS shard's row norms would allow
+    // with the fewest norm slots a layout has (4), so that the minimum over the ranks is one every rank can set
+    if (src->aux_lay.stride <= 0) out[3] = plan_q2max(plan_norm_unit(src->rmax_all, 4));
     return DPH_OK;
 }
 int dph_index_set_aux_layout(dph_index* h, const int32_t* in) {
@@ -621,25 +522,17 @@ int dph_index_set_aux_layout(dph_index* h, const int32_t* in) {
     if (!h || !in) return fail(DPH_E_ARG, "dph_index_set_aux_layout: null");
     if (h->sh->pq) return DPH_OK;        // a PQ index has no digits
     if (!h->sh->finalized) return fail(DPH_E_STATE, "dph_index_set_aux_layout: call dph_index_finalize first");
-    dph_aux_layout lay{};
-    lay.stride = in[0]; lay.n_norm = in[1]; lay.n_rep = in[2]; lay.q2max = in[3];
-    const bool ok_shape = (lay.stride == 0 && lay.n_norm == 0 && lay.n_rep == 0) || (lay.stride == 4 && lay.n_norm == 4 && lay.n_rep == 0) ||
-                          (lay.stride == 16 && lay.n_norm == 4 && lay.n_rep >= 0 && lay.n_rep <= 12) ||
-                          (lay.stride == 32 && lay.n_norm == 8 && lay.n_rep >= 0 && lay.n_rep <= DPH_AUX_REP_MAX);
-    if (!ok_shape || lay.q2max < 1 || lay.q2max > 64) return fail(DPH_E_ARG, "dph_index_set_aux_layout: not a layout dph_index_get_aux_layout returns");
-    for (int i = 0; i < lay.n_rep; ++i) {
-        if (in[4 + i] < 0 || in[4 + i] >= DPH_DIM) return fail(DPH_E_ARG, "dph_index_set_aux_layout: replica dimension out of range");
-        lay.rep_dim[i] = (short)in[4 + i];
-    }
+    plan_aux a{};
+    a.forced = true;
+    const int bad = plan_unpack_layout(in, &a.lay);
+    if (bad == 1) return fail(DPH_E_ARG, "dph_index_set_aux_layout: not a layout dph_index_get_aux_layout returns");
+    if (bad) return fail(DPH_E_ARG, "dph_index_set_aux_layout: replica dimension out of range");
     HIPCHK(hipSetDevice(h->device));
-    h->sh->aux_lay = lay;
-    h->sh->aux_lay_forced = true;
-    derive_aux_units(h->sh);
-    if (lay.stride > 0) {
-        // the forced clamp must serve this shard's norm unit (see derive_aux_units)
-        const int q2 = (int)floor(126.0 * 128.0 / ((double)h->sh->norm_unit * 27.7129));
-        if (lay.q2max > q2) return fail(DPH_E_ARG, "dph_index_set_aux_layout: q2max too large for this shard's row norms (take the minimum over the ranks)");
-    }
+    derive_aux_units(aux_facts(h->sh), &a);
+    set_aux_plan(h->sh, a);
+    // the forced clamp must serve this shard's norm unit (see derive_aux_units)
+    if (a.lay.stride > 0 && a.lay.q2max > plan_q2_limit(a.norm_unit))
+        return fail(DPH_E_ARG, "dph_index_set_aux_layout: q2max too large for this shard's row norms (take the minimum over the ranks)");
     const int rc = build_aux_rows(h->sh, nullptr);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(nullptr));
@@ -720,19 +613,9 @@ int dph_index_set_ivf(dph_index* h, int nlist, const float* centroids, const int
     h->sh->centroids.reset(); h->sh->tile_list.reset(); h->sh->list_tile0.reset();
     h->sc.ivf = dph_ivf_pass(); h->sc.uq = dph_unit_queue();
     // the unit scan needs every list to be one contiguous run of tiles (what ivf.build_list_major writes)
-    std::vector<int> tile0((size_t)nlist + 1, 0);
-    h->sh->lists_contiguous = nlist <= 65536 && h->sh->n_tiles < (int64_t)0x7fffffff;
-    for (int64_t t = 1; t < h->sh->n_tiles && h->sh->lists_contiguous; ++t) if (tile_list[t] < tile_list[t - 1]) h->sh->lists_contiguous = false;
-    h->sh->max_list_tiles = 0; h->sh->total_segs = 0;
-    if (h->sh->lists_contiguous) {
-        std::vector<int> cnt((size_t)nlist, 0);
-        for (int64_t t = 0; t < h->sh->n_tiles; ++t) cnt[(size_t)tile_list[t]]++;
-        for (int l = 0; l < nlist; ++l) {
-            tile0[(size_t)l + 1] = tile0[(size_t)l] + cnt[(size_t)l];
-            h->sh->max_list_tiles = std::max(h->sh->max_list_tiles, cnt[(size_t)l]);
-            h->sh->total_segs += (cnt[(size_t)l] + DPH_UNIT_TILES - 1) / DPH_UNIT_TILES;
-        }
-    }
+    std::vector<int> tile0;
+    const plan_list_facts geo = plan_list_geometry(tile_list, h->sh->n_rows, h->sh->n_tiles, nlist, tile0);
+    h->sh->lists_contiguous = geo.lists_contiguous; h->sh->max_list_tiles = geo.max_list_tiles; h->sh->total_segs = geo.total_segs;
     double cmax = 0.0;
     for (int l = 0; l < nlist; ++l) {
         double a = 0.0;
@@ -950,8 +833,7 @@ int dph_index_set_tuning(dph_index* h, const char* key, const int32_t* values, i
         h->sh->aux_lay_forced = false;
         if (h->sh->finalized) {              // the statistics stand: only the layout and the aux rows follow
             HIPCHK(hipSetDevice(h->device));
-            choose_aux_layout(h->sh);
-            derive_aux_units(h->sh);
+            set_aux_plan(h->sh, plan_aux_rows(aux_facts(h->sh), h->sh->aux_lay, false));
             const int rc = build_aux_rows(h->sh, nullptr);
             if (rc) return rc;
             HIPCHK(hipStreamSynchronize(nullptr));
@@ -1041,94 +923,23 @@ static int ensure_scratch(dph_index* h, int64_t n, int k_host) {
     return DPH_OK;
 }
 
-// The pre-pass ladder: strides of the sampled levels, coarse -> fine.  Every level scans each `stride`-th tile under
-// the bound of the previous one; the first runs cold (no bound: every sampled row is emitted), so it must be small
-// enough for the pair pool (the scan waves' fair share of it) and the buckets -- and a shard small enough for ITS full
-// scan to run cold needs no ladder at all.  The bound of the last level is what the full scan runs under: ~ kp * stride
-// rows per query row beat it whatever the shard size (plus ~2x as many that only pass the high-digit test).
-static void build_ladder(const dph_index* h, int qb, std::vector<int>& out) {
-    out.clear();
-    const int64_t nt = h->sh->n_tiles;
-    if (!h->tune.ladder.empty()) {
-        for (int v : h->tune.ladder) if (v > 1 && (nt + v - 1) / v >= 1) out.push_back(v);
-        return;
-    }
-    if (nt * DPH_TILE_ROWS <= DPH_POOL_MAX) return;             // every row fits the select pool: scan cold
-    // tiles a cold level may visit: the pair regions of the scan waves and the buckets must hold every sampled row.  The
-    // aim is ONE tile per scan workgroup: balanced, and the refine step of that level scores every (row, query) pair
-    const int64_t wave_share = (int64_t)DPH_POOL_CHUNKS * DPH_CHUNK_PAIRS / ((int64_t)h->tune.grid * 4);
-    const int64_t per_wg = wave_share / (DPH_TILE_ROWS * DPH_QGROUP * qb);
-    const int64_t cold_max = std::min<int64_t>((int64_t)h->tune.grid * per_wg / 2, DPH_BUCKET_CAP / DPH_TILE_ROWS - 64);
-    const int64_t cold_aim = std::min<int64_t>(h->tune.grid, cold_max);
-    const bool big = h->sh->n_rows >= 100000000ll;
-    const int fine = h->tune.fine_stride > 0 ? h->tune.fine_stride : (big ? 32 : 16);
-    const int ratio = big ? 16 : 8;
-    const int64_t s0 = std::max<int64_t>(2, (nt + cold_aim - 1) / cold_aim);          // stride that visits ~cold_aim tiles
-    std::vector<int64_t> up;             // fine -> coarse
-    int64_t s = std::max<int64_t>(2, fine);
-    while ((nt + s - 1) / s > cold_max) {
-        up.push_back(s);
-        int64_t next = s * ratio;
-        if ((nt + next - 1) / next < cold_aim) next = std::max<int64_t>(s0, s + 1);   // do not overshoot the cold level
-        s = next;
-    }
-    // s can run cold; the top level visits ~cold_aim tiles (if that sits too close above the level below, it replaces it)
-    if ((nt + s - 1) / s > cold_aim && s0 > s) { if (s0 >= s * 4) up.push_back(s); s = s0; }
-    if (!up.empty() && s < up.back() * 4) up.back() = s;
-    else up.push_back(s);
-    for (size_t i = up.size(); i-- > 0;) out.push_back((int)std::min<int64_t>(up[i], 1 << 30));
+static plan_ladder_facts ladder_facts(const dph_index* h) {
+    return plan_ladder_facts{h->sh->n_tiles, h->sh->n_rows, h->tune.grid, h->tune.fine_stride, h->tune.ladder.data(), (int)h->tune.ladder.size()};
 }
-
-// ---- unit scan of a list-major shard (dph_internal.h: DPH_PASS_MAX) --------------------------------------------------
-// Worth it when the lists are long: a unit pays a few microseconds of start-up (pop the queue, load its query fragments,
-// fill the pipeline) against ~1 us per 10 tiles of streaming.  Shards with many short lists (the reference's 2^20 lists)
-// keep the masked scan.
-static bool use_units(const dph_index* h, int nprobe) {
-    if (!h->sh->row_ids || nprobe <= 0 || !h->sh->lists_contiguous || h->tune.ivf_units == 0) return false;
-    return h->tune.ivf_units == 1 || h->sh->n_tiles / std::max(1, h->sh->nlist) >= 64;
-}
+// unit scan of a list-major shard, or the masked scan (dph_plan.h: use_units)
+static bool use_units(const dph_index* h, int nprobe) { return use_units(list_facts(h->sh), h->sh->row_ids != nullptr, h->tune.ivf_units, nprobe); }
 
 static int ensure_units(dph_index* h, int nprobe) {
-    const int64_t np = std::min<int64_t>(nprobe, h->sh->nlist);
-    const int64_t probes = (int64_t)DPH_PASS_MAX * np;                       // (query row, list) pairs of a pass
-    const int64_t extra = probes / DPH_UNIT_SLOTS + 1;                       // chunks beyond the first of a list
-    const int64_t chunk_cap = std::min<int64_t>(h->sh->nlist, probes) + extra;
-    const int64_t segs_max = (h->sh->max_list_tiles + DPH_UNIT_TILES - 1) / DPH_UNIT_TILES;
-    const int64_t unit_cap = h->sh->total_segs + extra * std::max<int64_t>(1, segs_max);
-    if (chunk_cap <= h->sc.uq.chunk_cap && unit_cap <= h->sc.uq.unit_cap) return DPH_OK;
+    const plan_unit_caps c = plan_unit_queue(list_facts(h->sh), nprobe);
+    if (c.chunk_cap <= h->sc.uq.chunk_cap && c.unit_cap <= h->sc.uq.unit_cap) return DPH_OK;
     h->sc.uq = dph_unit_queue();
-    if (chunk_cap > (1 << 22) || unit_cap > (1 << 26)) return fail(DPH_E_ARG, "unit scan: work queue too large for this nprobe");
-    HIPCHK(h->sc.uq.slot_q.alloc((size_t)chunk_cap * DPH_UNIT_SLOTS));
-    HIPCHK(h->sc.uq.unit_recs.alloc((size_t)unit_cap));
-    HIPCHK(h->sc.uq.unit_list_recs.alloc((size_t)chunk_cap));
-    HIPCHK(h->sc.uq.unit_frags.alloc((size_t)chunk_cap * 4 * DPH_QGROUP_FRAG_BYTES));
-    h->sc.uq.chunk_cap = (int)chunk_cap; h->sc.uq.unit_cap = (int)unit_cap;
+    if (c.too_large) return fail(DPH_E_ARG, "unit scan: work queue too large for this nprobe");
+    HIPCHK(h->sc.uq.slot_q.alloc((size_t)c.chunk_cap * DPH_UNIT_SLOTS));
+    HIPCHK(h->sc.uq.unit_recs.alloc((size_t)c.unit_cap));
+    HIPCHK(h->sc.uq.unit_list_recs.alloc((size_t)c.chunk_cap));
+    HIPCHK(h->sc.uq.unit_frags.alloc((size_t)c.chunk_cap * 4 * DPH_QGROUP_FRAG_BYTES));
+    h->sc.uq.chunk_cap = (int)c.chunk_cap; h->sc.uq.unit_cap = (int)c.unit_cap;
     return DPH_OK;
-}
-
-// One ladder level of a pass: flat / masked scans visit every stride-th tile of the shard; the unit scan visits the
-// tiles of every probed list whose index INSIDE the list is a multiple of the stride, and its cold level (stride =
-// longest list: tile 0 of every probed list) emits only the rows `rowmask` names, so that the cold sample of
-// DPH_PASS_MAX rows x nprobe lists fits the pair regions.
-struct ladder_level { int stride; unsigned rowmask; };
-
-static void build_ladder_units(const dph_index* h, int n_q, int nprobe, std::vector<ladder_level>& out, double* last_ratio) {
-    out.clear();
-    const int64_t np = std::min<int64_t>(nprobe, h->sh->nlist);
-    const int64_t probed = np * (h->sh->n_rows / std::max(1, h->sh->nlist));        // rows a query row scores (average)
-    *last_ratio = 1.0;
-    // small enough to run cold (every row of every probed list is emitted): a scan wave emits 1024 pairs per tile of a
-    // unit with full slot groups, so only shards of one- or two-tile lists qualify
-    if (h->sh->max_list_tiles <= 2 && (int64_t)n_q * probed <= (1 << 19) && probed <= DPH_POOL_MAX / 2) return;
-    int r = 32;                                                               // rows of a tile the cold level samples
-    while (r > 2 && (int64_t)n_q * np * r > (1 << 19)) r >>= 1;            // ~0.2 us of refine per 1000 pairs
-    const int64_t s0 = np * r;
-    const int fine = h->tune.fine_stride > 0 ? h->tune.fine_stride : 32;
-    std::vector<int> up;                                                      // fine -> coarse
-    for (int64_t s = std::max(2, fine); s < h->sh->max_list_tiles && probed / s >= 4 * s0; s *= 16) up.push_back((int)s);
-    out.push_back({std::max(1, h->sh->max_list_tiles), (1u << (r / 2)) - 1u});
-    for (size_t i = up.size(); i-- > 0;) out.push_back({up[i], 0xFFFFu});
-    *last_ratio = up.empty() ? std::max(1.0, (double)probed / (double)s0) : (double)up[0];
 }
 
 // clean = true: the rows are also written to q.x with non-finite rows replaced by their stand-in, q.nf flags them
@@ -1185,27 +996,10 @@ struct pass_args {
     float* D = nullptr; int64_t* I = nullptr; int32_t* status = nullptr; double* bound_out = nullptr;
     int32_t* ik_out = nullptr; int32_t* fail_out = nullptr;
     bool retry() const { return rowmap != nullptr; }
-    int C() const { return retry() ? DPH_SELECT_C_MAX : std::min(std::max(k + 32, 2 * k), DPH_SELECT_C_MAX); }   // candidates the select step re-scores
+    int C() const { return plan_select_C(k, retry()); }          // candidates the select step re-scores
 };
 // the two-stage form cuts a first-attempt pass behind its ladder (dph_search_prepare_dev / dph_search_finish_dev)
 enum search_stage { SEARCH_WHOLE, SEARCH_PREPARE, SEARCH_FINISH };
-
-// The full scan behind a FUSED finest ladder level of stride S (pass_scan_select): that level scanned tiles 0, S, 2S, ...; the full scan
-// visits the other `visit` tiles, visited index v -> tile v + v / (S - 1) + 1, and the kernel takes the quotient as
-// (v * m) >> 29 with m = ceil(2^29 / (S - 1)) (dph_scan.hip, tile_of).  With err = m (S - 1) - 2^29 that is exact as long as
-// v * err < 2^29 (the fraction the multiply adds stays below 1 / (S - 1)).  Returns the number of tiles to visit and the
-// multiplier, or 0 when the scan is not to be fused (no bounded level, a shard of a few tiles, a multiply that would not be
-// exact or would overflow).
-static int64_t fused_scan_plan(int64_t n_tiles, int stride, unsigned* m_out) {
-    if (stride < 2 || n_tiles <= 4 * (int64_t)stride) return 0;
-    const unsigned d = (unsigned)stride - 1u;
-    const unsigned m = (unsigned)(((1ull << 29) + d - 1) / d);
-    const uint64_t err = (uint64_t)m * d - (1ull << 29);
-    const int64_t visit = n_tiles - (n_tiles + stride - 1) / stride;
-    if ((uint64_t)visit * (err ? err : 1) >= (1ull << 29) || (uint64_t)visit * m >= (1ull << 62)) return 0;
-    *m_out = m;
-    return visit;
-}
 
 // what every coarse search of a shard shares: its quantizer, the query rows, the score scratch (the caller adds masks and gate)
 static dph_coarse_args coarse_args(const dph_shard& sh, const float* x, int q0, int n_q, int nprobe, float* scores) {
@@ -1255,18 +1049,15 @@ static int pass_ladder(dph_index* h, dph_pass p, const pass_args& a, hipStream_t
     std::vector<ladder_level> levels;
     double last_ratio = 1.0;             // rows of the shard (of the probed lists) per row of the last level's sample
     if (units) {
-        build_ladder_units(h, p.n_q, a.nprobe, levels, &last_ratio);
+        build_ladder_units(list_facts(h->sh), h->tune.fine_stride, p.n_q, a.nprobe, levels, &last_ratio);
     } else {
         std::vector<int> strides;
-        build_ladder(h, p.qb, strides);
+        build_ladder(ladder_facts(h), p.qb, strides);
         for (int v : strides) levels.push_back({v, 0xFFFFu});
         if (!strides.empty()) last_ratio = strides.back();
     }
-    // the bound of a level is its kp-th best sampled score: ~kp * last_ratio rows beat it in the full scan, and
-    // that must cover the C candidates the select step wants to re-score
-    int kp = h->tune.sample_kp;
-    if (!levels.empty()) kp = std::max(kp, (int)((double)a.C() * 1.5 / last_ratio) + 8);
-    if ((int)levels.size() + 1 > DPH_UNIT_LAUNCHES) return fail(DPH_E_STATE, "ladder deeper than the unit work-queue heads");
+    const int kp = plan_kp(h->tune.sample_kp, !levels.empty(), a.C(), last_ratio);
+    if (!plan_ladder_fits(levels.size())) return fail(DPH_E_STATE, "ladder deeper than the unit work-queue heads");
     *b = pass_bound();
     for (size_t i = 0; i < levels.size(); ++i) {
         const int stride = levels[i].stride;
@@ -1373,8 +1164,8 @@ static int search_core(dph_index* h, const float* x_dev, int64_t n, const pass_a
     for (int64_t q0 = 0; q0 < n;) {
         const int64_t left = n - q0;
         const bool units = use_units(h, call.nprobe);               // a unit pass serves up to DPH_PASS_MAX rows
-        const int qb = units ? 1 : ((left > DPH_QROWS && h->tune.max_qb >= 2) ? 2 : 1);
-        const int nq = (int)std::min<int64_t>(left, units ? (int64_t)DPH_PASS_MAX : (int64_t)DPH_QROWS * qb);
+        int qb = 1;
+        const int nq = plan_pass_rows(left, units, h->tune.max_qb, &qb);
         dph_pass p = make_pass(h, h->sc.q_main, x_dev, (int)q0, nq, qb);
         pass_args a = call;
         if (a.tau_ext) a.tau_ext += q0;

@@ -30,10 +30,9 @@
 #include <vector>
 
 #include "dph_internal.h"
+#include "dph_plan.h"
 
-#define PQ_THREADS 1024
-#define PQ_SEG 12288                  // codes per segment (M <= 96: 96 KiB of LUT + 48 KiB of keys); halved for larger M (LDS budget).  12288: a row-major unit of the released shape (64 lists, ~10 k codes) is ONE segment -- one k-th selection per unit instead of two (8192: r1-r4)
-#define PQ_FINAL_CAP 4096             // candidates the final sort takes (k + boundary ties)
+// (PQ_THREADS, PQ_SEG, PQ_FINAL_CAP, PQ_LM_CHUNK, PQ_GROUP: dph_geometry.h -- the capacity rules of dph_plan.h are made of them)
 
 __device__ __forceinline__ unsigned pq_key(float s) {
     const unsigned b = __float_as_uint(s);
@@ -240,7 +239,6 @@ __global__ __launch_bounds__(256) void pq_lut_kernel(const float* __restrict__ x
 // one thread per list: every query row of the pass whose bit is set in the list's probe mask becomes a pair -- one pair per CHUNK of
 // PQ_LM_CHUNK segments of the list (round 6: work cut by code count; a list of millions of codes among lists of thousands is many
 // units of many workgroups, not one workgroup's).  Record: (list, row | chunk << 10); the rows of a pass fit 10 bits (DPH_PASS_MAX).
-#define PQ_LM_CHUNK 4
 static_assert(DPH_PASS_MAX <= 1024, "pair records keep the row in 10 bits");
 __global__ __launch_bounds__(256) void pq_pairs_kernel(const unsigned* __restrict__ listmask, int mask_words, int nlist,
                                                        const int64_t* __restrict__ list_off, int seg, int2* __restrict__ pairs,
@@ -484,7 +482,6 @@ __global__ __launch_bounds__(PQ_THREADS, 1) void pq_adc_kernel(pq_scan_args a) {
 // lists are known; a workgroup of the scan pops a record, loads the row's table, rebuilds the group's prefix sums (64 offsets)
 // and scores its segment only -- dis0 of just the lists that segment touches.  A uniform index gives one unit per group: the
 // same work as before.
-#define PQ_GROUP 64
 // one wave per (row, group): total codes of the group's lists -> ceil(total / seg) unit records (none for an empty group)
 __global__ __launch_bounds__(256) void pq_units_kernel(const int* __restrict__ probe, int probe_stride, int units_per_row, int n_groups,
                                                        const int64_t* __restrict__ list_off, int seg, int2* __restrict__ units,
@@ -974,12 +971,7 @@ int dph_pq_set_list_sizes(dph_pq* p, const int64_t* sizes) {
     }
     if (p->h_list_off[(size_t)p->nlist] != p->ntotal) return fail(DPH_E_ARG, "PQ index: list sizes do not add up to ntotal");
     HIPCHK(hipMemcpy(p->list_off, p->h_list_off.data(), ((size_t)p->nlist + 1) * 8, hipMemcpyHostToDevice));
-    {
-        std::vector<int64_t> srt(sizes, sizes + p->nlist);
-        std::sort(srt.begin(), srt.end(), [](int64_t x, int64_t y) { return x > y; });
-        p->h_top_prefix.assign((size_t)p->nlist + 1, 0);
-        for (int l = 0; l < p->nlist; ++l) p->h_top_prefix[(size_t)l + 1] = p->h_top_prefix[(size_t)l] + srt[(size_t)l];
-    }
+    plan_pq_top_prefix(sizes, p->nlist, p->h_top_prefix);
     p->s = pq_scratch();                                   // (the scratch is sized from the list lengths)
     p->lists_set = true;
     p->finalized = false;
@@ -1110,24 +1102,9 @@ int64_t dph_pq_ntotal(const dph_pq* p) { return p ? p->ntotal : 0; }
 int dph_pq_nlist(const dph_pq* p) { return p ? p->nlist : 0; }
 const float* dph_pq_A_host(const dph_pq* p) { return p ? p->h_A.data() : nullptr; }
 
-static constexpr int pq_seg(int M) { return M <= 96 ? PQ_SEG : PQ_SEG / 2; }
-// many short lists ON AVERAGE: the work is grouped by query row (pq_adc_rows_kernel) and cut by code count, so a list hundreds of times
-// the mean is several units of several workgroups.  (A group's 64 lists are one sequence indexed with 32-bit ints: 2^24 codes per list.)
-static bool pq_by_rows(const dph_pq* p) { return p->ntotal / p->nlist < 2048 && p->max_list < ((int64_t)1 << 24); }
-// codes a query row can meet at most: those of its nprobe LONGEST lists, not nprobe x the longest (dph_pq_set_list_sizes fills the
-// prefix sums, and no index is searched without it)
-static int64_t pq_row_codes_max(const dph_pq* p, int nprobe) { return p->h_top_prefix[(size_t)std::min(nprobe, p->nlist)]; }
-// units / segments a query row can meet at most: one (partial) segment per group + the codes of its nprobe longest lists cut into segments
-static int64_t pq_row_units_max(const dph_pq* p, int nprobe) { return (nprobe + PQ_GROUP - 1) / PQ_GROUP + pq_row_codes_max(p, nprobe) / pq_seg(p->M) + 1; }
-// dynamic LDS of the ADC scans: the row's tables [M][256], the keys of a segment, histogram, wave partials, the queue item
-static constexpr size_t pq_lds_bytes(int M) { return (size_t)M * 1024 + (size_t)pq_seg(M) * 4 + 264 * 4 + 16 * 8 + 16; }
-// ... and the most any M that dph_pq_alloc accepts asks for: the allowance is granted once per kernel and device, whatever the handle
-static constexpr size_t pq_lds_bytes_max() {
-    size_t mx = 0;
-    for (int M = 16; M <= 128; M += 16) if (DPH_DIM % M == 0 && pq_lds_bytes(M) > mx) mx = pq_lds_bytes(M);
-    return mx;
-}
-static_assert(pq_lds_bytes_max() <= 160 * 1024, "the ADC scans' tables and keys must fit the 160 KiB of LDS of a CU");
+// the scan's plan (dph_plan.h: segment length, row-major or list-major work, LDS, capacities) from this index's lists
+static plan_pq_facts pq_facts(const dph_pq* p) { return plan_pq_facts{p->M, p->ntotal, p->nlist, p->max_list, p->h_top_prefix.data()}; }
+static bool pq_by_rows(const dph_pq* p) { return pq_by_rows(pq_facts(p)); }
 // (one workgroup per CU either way: __launch_bounds__(PQ_THREADS, 1); the launches pass pq_lds_bytes(p->M))
 static void pq_allow_lds(int device) {
     DPH_ALLOW_LDS(pq_adc_kernel<6>, pq_lds_bytes_max(), device);
@@ -1141,24 +1118,8 @@ static int pq_ensure(dph_pq* p, int rows, int k, int nprobe) {
     rows = std::max(rows, p->s.cap_rows); k = std::max(k, p->s.cap_k); nprobe = std::max(nprobe, p->s.cap_nprobe);
     p->s = pq_scratch();
     pq_scratch& s = p->s;
-    // every segment may append its k best -- or, in the row-major scan (pq_segment_finish<true>: the bound of a long segment is the k-th of
-    // a 1024-key sample), about k * seg / 1024 keys: twice that is reserved
-    const bool by_rows = pq_by_rows(p);
-    // (the scratch serves every later call with k' <= k without a new allocation: the sampled rule's share for min(k, 128) counts even when
-    // THIS k is beyond it)
-    const int64_t per_seg = by_rows ? std::max<int64_t>(k, (int64_t)std::min(k, PQ_THREADS / 8) * (pq_seg(p->M) / PQ_THREADS) * 2) : k;
-    // segments a row can meet: row-major, (partial) segments of its groups; list-major, every probed list on its own
-    const int64_t codes_row = pq_row_codes_max(p, nprobe);
-    const int64_t segs_row = by_rows ? pq_row_units_max(p, nprobe) : (int64_t)nprobe + codes_row / pq_seg(p->M);
-    // + 512: the count above the k-th of a 1-in-12 sample has a geometric tail -- for k = 1, P(more than m) = (11/12)^m: m = 64 was
-    // crossed once in 4000 cold segments, 512 once in 10^19
-    int64_t cap = segs_row * per_seg + 512;
-    const int64_t budget = ((int64_t)2 << 30) / 8 / rows;                // at most 2 GiB of candidates per pass
-    cap = std::max<int64_t>(std::min(cap, budget), 4 * (int64_t)k + 64);
-    s.cand_cap = (int)std::min<int64_t>(cap, 1 << 30);
-    // list-major pairs: one per chunk of PQ_LM_CHUNK segments of a probed list -- at most nprobe + (codes of the nprobe longest lists) / chunk per row
-    s.pair_cap = (int)std::min<int64_t>((int64_t)rows * (nprobe + (by_rows ? 0 : codes_row / ((int64_t)pq_seg(p->M) * PQ_LM_CHUNK))), 1 << 28);
-    s.unit_cap = by_rows ? (int)std::min<int64_t>((int64_t)rows * pq_row_units_max(p, nprobe), 1 << 28) : 0;
+    const plan_pq_caps caps = plan_pq_scan(pq_facts(p), rows, k, nprobe);
+    s.cand_cap = caps.cand_cap; s.pair_cap = caps.pair_cap; s.unit_cap = caps.unit_cap;
     if (s.xp.alloc((size_t)rows * DPH_DIM) != hipSuccess || s.lut.alloc((size_t)rows * p->M * 256) != hipSuccess ||
         s.scores.alloc((size_t)rows * p->nlist) != hipSuccess || s.listmask.alloc((size_t)p->nlist * DPH_UNIT_WORDS) != hipSuccess ||
         s.counters.alloc(pq_scratch::counter_bytes(rows, 4) / 4) != hipSuccess ||

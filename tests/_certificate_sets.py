@@ -97,8 +97,9 @@ def _aligned_row(mu, sign, dims, cap2, pin, pin_code):
 
 
 def choose_layout(xb, mode):
-    """choose_aux_layout (csrc/dph_api.hip) for a forced stride `mode` (4 or 16), restated: rogue dimensions = mean code further than
-    1.2 x 3.5 median spreads from the median mean; the 12 replica slots of stride 16 are dealt out by largest remainder of the ratios."""
+    """choose_aux_layout (csrc/dph_plan.h) for a forced stride `mode` (4 or 16), restated: rogue dimensions = mean code further than
+    1.2 x 3.5 median spreads from the median mean; the 12 replica slots of stride 16 are dealt out by largest remainder of the ratios.
+    Held against the real rule on the CPU, on every shard of this module (tests/test_plan.py)."""
     xi = xb.astype(np.float64)
     mean = xi.mean(0)
     sd = np.sqrt(np.maximum((xi * xi).mean(0) - mean * mean, 0.0))

@@ -366,6 +366,16 @@ def test_sampled_segment_bound_never_drops_a_member_of_the_top_k():
         assert bound <= true_top[0] or len(allk) < k                       # the bound stayed a lower bound of the true k-th
 
 
+def _pq_reserved_per_segment(k):
+    """what pq_ensure reserves for one segment of a row-major index with M = 96: the per-segment share of the real rule
+    (csrc/dph_plan.h, through tests/_plan.py) + the sample's tail"""
+    from tests import _plan as P
+    sizes = P.list_sizes("uniform", 4096)                   # 1000 codes per list: the row-major scan
+    plan = P.pq_scan(96, sizes, P.pq_top_prefix(sizes), 1024, k, 64)
+    assert plan["by_rows"] and plan["seg"] == 12288
+    return plan["per_seg"] + P.constants()["PQ_SAMPLE_TAIL"]
+
+
 def test_sampled_segment_bound_appends_within_the_reserved_capacity():
     """What a COLD segment (row bound still -inf) appends under the sampled rule, against what pq_ensure reserves for it
     (2 k seg / 1024 per segment + 512 per row).  A segment is a sequence of lists, each with its own <x', centroid> offset: the row's
@@ -383,7 +393,7 @@ def test_sampled_segment_bound_appends_within_the_reserved_capacity():
         keys = [np.concatenate([rest, top]), np.concatenate([top, rest]), np.sort(np.concatenate([rest, top]))][trial % 3]
         sample = keys[(np.arange(1024) * n) // 1024]
         count = int((keys >= np.sort(sample)[-k]).sum())
-        reserved = 2 * k * (12288 // 1024) + 512
+        reserved = _pq_reserved_per_segment(k)
         assert count <= reserved, (trial, k, n, count, reserved)
         worst_new = max(worst_new, count - 2 * k * 12)
         old = keys[np.arange(1024) * (n // 1024)]
