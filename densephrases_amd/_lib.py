@@ -507,7 +507,16 @@ class Shard:
                                 C.c_void_p(status_ptr), C.c_void_p(stream)))
 
     def search_sample_dev(self, x_ptr: int, n: int, top_ptr: int, stream: int = 0):
-        """Phase 1 of the sharded search: the 16 best pre-pass sample scores per row -> int32 [n,16] (dph.h)."""
+        """Phase 1 of the sharded search: the 16 best pre-pass sample scores per row -> int32 [n,16] (dph.h).
+
+        What the call shares is the result of the LAST ladder level of every pass: the 16 best exact integer scores among the
+        non-outlier rows that level emitted, in any order, INT_MIN where there are fewer (no level at all -- a shard of at most
+        8192 rows under the derived ladder -- gives INT_MIN everywhere).  The call carries no k: the levels in front of the last
+        are cut at kp = plan_kp(sample_kp, C of k = 1), the last one always at 16.  Under a ladder whose strides nest that is
+        simply the 16 best non-outlier rows of the tiles t % last_stride == 0; strides that do not nest (tuning key "ladder",
+        e.g. 7, 2) share only every lcm-th tile between two levels, and fewer than 16 rows of the last level may pass the bound
+        of the one before.  The derived ladder depends on the width of the pass (128 or 256 rows), so a call of 300 rows may
+        sample its last 44 rows differently from its first 256.  tests/_shard_merge_ref.py restates all of it."""
         _chk(lib.dph_search_sample_dev(self._h, C.c_void_p(x_ptr), int(n), C.c_void_p(top_ptr), C.c_void_p(stream)))
 
     def search_bounded_dev(self, x_ptr: int, n: int, k: int, tau_ptr: int, D_ptr: int, I_ptr: int, status_ptr: int,

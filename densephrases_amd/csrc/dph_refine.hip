@@ -236,19 +236,23 @@ __global__ __launch_bounds__(THR_THREADS) void dph_threshold_kernel(
     }
     if (top_out) {
         // the KEEP best sampled scores themselves (any order; INT_MIN where the sample holds fewer): what a rank shares
-        // so that the bound can be taken over the union of all ranks' samples (dph_union_bounds_kernel); kp == KEEP here
+        // so that the bound can be taken over the union of all ranks' samples (dph_union_bounds_kernel); kp == KEEP here.
+        // Only the scores strictly above the KEEP-th take a slot by atomic -- there are fewer than KEEP of them (with fewer than KEEP
+        // keys in the bucket ans is 0 and that is every score) -- and the KEEP-th value itself fills the rest: were its ties to race
+        // for the slots as well, they could push a better score out, and the multiset shared would no longer be the KEEP best.
         if (tid == 0) top_cnt = 0;
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < THR_PER; ++j) {
-            if (u[j] != 0u && u[j] >= ans) {
+            if (u[j] > ans) {
                 const unsigned slot = atomicAdd(&top_cnt, 1u);
                 if (slot < (unsigned)DPH_SAMPLE_KEEP) top_out[(int64_t)qi * DPH_SAMPLE_KEEP + slot] = (int)(u[j] ^ 0x80000000u);
             }
         }
         __syncthreads();
+        const int fill = (int)(ans ^ 0x80000000u);          // ans == 0: INT_MIN, the padding
         for (unsigned t = top_cnt + tid; t < (unsigned)DPH_SAMPLE_KEEP; t += THR_THREADS)
-            top_out[(int64_t)qi * DPH_SAMPLE_KEEP + t] = (int)0x80000000;
+            top_out[(int64_t)qi * DPH_SAMPLE_KEEP + t] = fill;
     }
 }
 
