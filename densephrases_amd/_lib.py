@@ -124,6 +124,8 @@ def _load() -> C.CDLL:
         "dph_index_get_transform": (C.c_int, [vp, vp]),
         "dph_index_attach_doc_rows": (C.c_int, [vp, i64]),
         "dph_pq_encode_dev": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+        "dph_pq_train_step_dev": (C.c_int, [i32, vp, i64, i32, vp, vp, vp, vp, i32, vp]),
+        "dph_pq_decode_dev": (C.c_int, [i32, vp, i64, i32, vp, vp, vp]),
         "dph_index_fill_pq_dev": (C.c_int, [vp, i64, vp, vp, vp, vp]),
         "dph_index_get_pq_list_sizes": (C.c_int, [vp, vp]),
         "dph_index_download_pq_codes": (C.c_int, [vp, i64, i64, vp, vp]),
@@ -152,7 +154,7 @@ EXPORTED = ["dph_abi_version", "dph_last_error", "dph_device_count", "dph_index_
             "dph_index_set_tuning", "dph_scan_counters", "dph_debug_wave_pairs", "dph_index_rehome_rows", "dph_index_gather_rows_dev", "dph_kmeans_step_dev", "dph_index_stored_rows", "dph_index_set_id_groups", "dph_ivf_assign_dev", "dph_index_assign_dev", "dph_index_make_list_major", "dph_score_vecs_dev", "dph_score_vecs_bwd_dev", "dph_dense_logits_dev",
             "dph_profile_enable", "dph_profile_read", "dph_profile_read_all", "dph_index_set_row_ids",
             "dph_index_set_ivf", "dph_search_ivf", "dph_search_ivf_dev", "dph_index_create_pq", "dph_index_set_pq",
-            "dph_index_set_pq_list_sizes", "dph_index_upload_pq_codes", "dph_index_get_transform", "dph_index_attach_doc_rows", "dph_pq_encode_dev",
+            "dph_index_set_pq_list_sizes", "dph_index_upload_pq_codes", "dph_index_get_transform", "dph_index_attach_doc_rows", "dph_pq_encode_dev", "dph_pq_train_step_dev", "dph_pq_decode_dev",
             "dph_index_fill_pq_dev", "dph_index_get_pq_list_sizes", "dph_index_download_pq_codes", "dph_index_create_twin",
             "dph_stream_create_cu_range", "dph_stream_destroy", "dph_search_prepare_dev", "dph_search_finish_dev"]
 

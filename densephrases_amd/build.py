@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["dph_api.hip", "dph_scan.hip", "dph_quant.hip", "dph_refine.hip", "dph_select.hip", "dph_window.hip",
-           "dph_ivf.hip", "dph_build.hip", "dph_kmeans.hip", "dph_pq.hip", "dph_pq_encode.hip"]
+           "dph_ivf.hip", "dph_build.hip", "dph_kmeans.hip", "dph_pq.hip", "dph_pq_encode.hip", "dph_pq_train.hip"]
 HEADERS = [os.path.join(CSRC, "dph_internal.h"), os.path.join(CSRC, "dph_geometry.h"), os.path.join(CSRC, "dph_plan.h"),
            os.path.join(HERE, "..", "include", "dph.h"), os.path.join(HERE, "..", "include", "dph_debug.h")]
 OUT = os.path.join(CSRC, "libdph.so")

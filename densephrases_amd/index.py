@@ -102,6 +102,9 @@ class MIPS(object):
         IndexPreTransform(OPQMatrix) -> IndexIVFPQ (``trained.faiss`` of build_phrase_index.py:96-142): the rows are uploaded as
         for the flat index, encoded where they lie (densephrases_amd/pq_build.py: the add step of :145-153 on the GPU) and
         released; from there on the object is what a finished ``index.faiss`` gives.  ``"save"`` also writes that file.
+        ``pq={"train": {"nlist": 4096, "M": 96, ...}[, "save_trained": path, "save": path]}`` trains that index first, on the resident
+        rows (densephrases_amd/pq_train.py: the train step of :96-142 on the GPU, its keyword arguments), optionally writes it as
+        ``trained.faiss``, and goes on as above.  Not together with ``"trained"``.
         Not together with ``ivf=`` or ``world > 1``.
 
         ``window_rows`` (only with an OPQ + IVFPQ ``index_path``; ValueError together with a flat index, ``ivf=`` or ``pq=``) picks
@@ -133,6 +136,10 @@ class MIPS(object):
             raise ValueError("MIPS: world > 1 needs a torch.distributed process group (or a `dist` object)")
         if pq is not None and (ivf is not None or self.world > 1):
             raise ValueError("MIPS(pq=...): not together with ivf= (the trained index brings its own lists) or world > 1 (sharded compression is not built)")
+        if pq is not None and "train" in pq and "trained" in pq:
+            raise ValueError('MIPS(pq=...): "train" builds the trained index itself, not together with "trained"')
+        if pq is not None and "train" not in pq and "trained" not in pq:
+            raise ValueError('MIPS(pq=...): needs "trained" (a trained, empty index) or "train" (the arguments of pq_train.train_index_resident)')
         if window_rows not in (None, "reconstructed", "raw", "reference"):
             raise ValueError(f'MIPS(window_rows={window_rows!r}): None, "reconstructed", "raw" or "reference"')
         if window_rows is not None and (ivf is not None or pq is not None):
@@ -237,14 +244,15 @@ class MIPS(object):
 
     def _build_pq(self, store, device: int, pq: dict):
         """``pq={"trained": ...}``: the dump's rows go to HBM like a flat shard, add_with_ids_resident turns them into the codes and
-        lists of the trained index (ids = the dump's own: row number, or the id groups of a merged dump), the flat rows are released."""
+        lists of the trained index (ids = the dump's own: row number, or the id groups of a merged dump), the flat rows are released.
+        ``pq={"train": ...}``: pq_train.train_index_resident makes that trained index from the resident rows first."""
         import torch
         from . import faiss_io
         from .pq_build import add_with_ids_resident
-        trained = pq["trained"]
+        trained = pq.get("trained")
         if isinstance(trained, (str, os.PathLike)):
             trained = faiss_io.read_index(str(trained))
-        if int(trained.ntotal) != 0:
+        if trained is not None and int(trained.ntotal) != 0:
             raise ValueError(f"MIPS(pq=...): the trained index must be empty, it holds {trained.ntotal} vectors")
         n = store.n_rows
         self.row_lo, self.row_hi = 0, n
@@ -253,6 +261,12 @@ class MIPS(object):
         try:
             flat.set_codec(store.offset, store.scale)
             self._upload(store, 0, n)
+            if trained is None:
+                from .pq_train import train_index_resident
+                trained = train_index_resident(flat, device=device, offset=store.offset, scale=store.scale, **dict(pq["train"]))
+                if pq.get("save_trained"):
+                    os.makedirs(os.path.dirname(os.path.abspath(str(pq["save_trained"]))), exist_ok=True)
+                    faiss_io.write_index(trained, str(pq["save_trained"]))
             ids = None
             groups = store.id_groups(0, n)
             if groups is not None:

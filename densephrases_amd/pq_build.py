@@ -3,7 +3,7 @@ IndexPreTransform(OPQMatrix) -> IndexIVFPQ (the reference's build_phrase_index.p
 
 Input: a parsed trained index (densephrases_amd.faiss_io.read_index of ``trained.faiss``: OPQ matrix, coarse centroids, codebooks, empty
 lists) and the dump's rows; output: a resident, searchable PQ ``Shard`` -- the rows never leave HBM as fp32, their codes are built
-where they lie (csrc/dph_pq_encode.hip).  OPQ / k-means / codebook TRAINING is not done here."""
+where they lie (csrc/dph_pq_encode.hip).  The trained index itself: densephrases_amd/pq_train.py."""
 from __future__ import annotations
 
 from typing import Optional

@@ -275,7 +275,7 @@ int dph_index_get_transform(dph_index* h, float* A_out /* [768*768] */);
  * Range-sharded: a rank attaches the rows of the documents of its own (document-aligned) range; windows never leave a document. */
 int dph_index_attach_doc_rows(dph_index* h, int64_t n_doc_rows);
 /* ---- filling such an index on the device: index.add_with_ids behind a TRAINED index (build_phrase_index.py:145-153; add_to_index,
- * :156-279, feeds it the dump rows; training itself -- :96-142 -- is not replaced).  The handle needs its parameters (dph_index_set_pq), no codes.
+ * :156-279, feeds it the dump rows; training itself -- :96-142 -- is dph_pq_train_step_dev below).  The handle needs its parameters (dph_index_set_pq), no codes.
  *   dph_pq_encode_dev            replaces the encoding half of add_with_ids (:145-153).  x_dev [n,768] fp32 -> list_dev[n], codes_dev[n,M]:
  *                                x' = fp32(A x + b) (float64 accumulation, one rounding); list = arg-max_l <x', c_l> in the float64 order, ties to
  *                                the lowest list (fused MFMA estimate; rows inside the fp32 error band, exact ties included, re-decided in float64
@@ -295,6 +295,21 @@ int dph_pq_encode_dev(dph_index* h, const float* x_dev, int64_t n, int32_t* list
 int dph_index_fill_pq_dev(dph_index* h, int64_t n /* == ntotal */, const int32_t* list_dev, const uint8_t* codes_dev, const int64_t* ids_dev, void* stream);
 int dph_index_get_pq_list_sizes(dph_index* h, int64_t* sizes /*[nlist]*/);
 int dph_index_download_pq_codes(dph_index* h, int64_t pos0, int64_t n, uint8_t* codes, int64_t* ids);
+/* ---- training such an index on the device (index.train, build_phrase_index.py:96-142): the sub-space Lloyd step the OPQ alternation and the
+ * residual PQ are made of (densephrases_amd/pq_train.py drives them).  Stateless: a device id, device pointers, no handle; scratch lives for the
+ * call.  M as dph_index_create_pq admits it (a multiple of 16 that divides 768, M <= 128), dsub = 768 / M, codebooks [M,256,dsub] fp32.
+ *   dph_pq_train_step_dev        x_dev [n,768] fp32 (already rotated; for the IVFPQ stage already residuals), 0 < n < 2^31.  Under the INPUT codebooks:
+ *                                codes_dev[r][m] = arg-min_j ||w_mj||^2 - 2 <x_rm, w_mj>, the float64 value with products and sums sequential in t, ties
+ *                                to the lowest j (the kernel of dph_pq_encode_dev); counts_dev[m][j] = rows with that code; row_err_dev[r] (NULL: not
+ *                                wanted) = sum_t (x[r][t] - w[code][t])^2 in float64, t ascending.  With update != 0 the codebooks are then replaced:
+ *                                w_mj = fp32(float64 sum of the members' slices, taken in ASCENDING ROW ORDER, / count); a codeword without members
+ *                                keeps its value.  A pure function of its inputs: two calls give the same bytes.  x, codes and the codebooks 16-byte
+ *                                aligned.  Synchronous on `stream`.
+ *   dph_pq_decode_dev            y_dev[r] = concat_m w[m][codes_dev[r][m]], fp32 [n,768]; asynchronous on `stream`. */
+int dph_pq_train_step_dev(int device, const float* x_dev, int64_t n, int M, float* pq_centroids_dev /* in/out */,
+                          uint8_t* codes_dev /* [n,M]: arg-min under the INPUT codebooks */, uint32_t* counts_dev /* [M,256] */,
+                          double* row_err_dev /* [n] under the INPUT codebooks, or NULL */, int update /* 0 = assign only */, void* stream);
+int dph_pq_decode_dev(int device, const uint8_t* codes_dev, int64_t n, int M, const float* pq_centroids_dev, float* y_dev, void* stream);
 
 /* ---- faiss reconstruct (index.py:31, 286, 296) ---- de-quantised fp32 row of a global id */
 int dph_reconstruct(dph_index* h, int64_t id, float* out768);
